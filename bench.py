@@ -12,14 +12,18 @@ clip + AdamW, over one synthetic batch of B = 8 clips x 30 s (16 kHz) + 128 text
 resident in HBM before the timed region.  Weights: seeded random init at the true architecture shapes (no
 checkpoints offline); data: synthetic.  Weak scaling: per-GPU work is fixed.
 
-The JSON line also carries
+A plain run does only what the headline figure needs: set-up, --warmup untimed steps, --steps timed steps, the JSON line
+(`value`, `ms_per_step` = wall milliseconds of one timed step, ...).  With --full the line also carries
   roofline     — the dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs of every launch / its duration,
                  timed live with HIP events on the launch stream inside the timed region, vs 2.5 PFLOP/s.  The events
                  are attached to the GEMM dispatches themselves (hipExtLaunchKernelGGL) of every 4th timed step
                  (--prof-every; `roofline.profiled_steps`): a timed dispatch costs ~1.4 us, and the steps in between
-                 run exactly as a training step does;
+                 run exactly as a training step does.  roofline.traffic comes from two rocprofv3 --pmc sub-runs;
+  parity       — the committed full-depth parity record of the workload, and (C2) a live one measured in the run;
   cpu_baseline — the CPU oracle (oracle/reference_cpu.py, a port of the reference path) timed on this box's
                  host cores on a bounded sample of the same workload (rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -158,6 +162,8 @@ def run_inference(args, wl, dev) -> None:
     t_all_max = float(mine.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": out})
     ms_tok = (t_all - t_prefill) / (new - 1) * 1e3
     wbytes = llm_weight_bytes(cfg)
     ach = wbytes / (ms_tok * 1e-3) / 1e9
@@ -537,6 +543,27 @@ def _opt_get(opt: str, key: int, default: int) -> int:
     return default
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6       # --dump-outputs: array data in all (+ 128 header bytes per .npy), under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy for every array, float32 (float64 for integer outputs, exact), DUMP_MAX_BYTES of data at most.  An
+    array larger than its share of the budget is written flat as a fixed sample: the elements at sorted indices drawn by
+    numpy.random.default_rng(0), the same positions in every run and every build, so that two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        exact = not t.is_floating_point()
+        cap = share // (8 if exact else 4)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), (t.double() if exact else t.float()).numpy())
+
+
 def self_launch(n: int) -> int:
     """Re-execute this command line as n ranks of one node: `python -m torch.distributed.run --nnodes=1 --nproc-per-node n
     --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`."""
@@ -567,18 +594,25 @@ def main():
                     help="transposed weight copies of the frozen LLM for the backward pass: made on the fly on a side stream (on), resident (off), "
                          "or resident unless the LLM exceeds a third of the GPU's memory (auto, the model's default)")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the live HIP-event roofline of the GEMM kernel and its "
+                         "rocprofv3 traffic sub-runs, the committed and live parity records, the CPU-oracle baseline (off: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, projector weights and gradients; generated tokens "
+                         "for the inference workloads) as DIR/<name>.npy, float32 / float64, at most 64 MB (fixed seeded samples of larger arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle baseline")
     ap.add_argument("--cpu-baseline-full", default=None, metavar="OUT.json",
                     help="CPU only: time ONE WHOLE step of the workload at B = 1 through the oracle (all layers) and write the record")
-    ap.add_argument("--no-prof", action="store_true", help="skip the live HIP-event timing of the GEMM kernel")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the live HIP-event timing of the GEMM kernel")
     ap.add_argument("--parity-live", action="store_true",
                     help="with the cpu_baseline leg: also run its weights and B = 1 batch through the HIP path at full depth and report the measured "
-                         "distances as parity.live (default on for the plain c2 line; adds ~10 s)")
+                         "distances as parity.live (default on for the c2 line under --full; adds ~10 s)")
     ap.add_argument("--no-parity-live", action="store_true", help="never run the live parity check")
     ap.add_argument("--no-prefix-skip", action="store_true",
                     help="A/B: run the LLM backward on every row (uvx_llm_bwd_train) instead of from the first audio token (uvx_llm_bwd_train_from)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="quote roofline.traffic from the committed PMC summary instead of measuring it in two rocprofv3 --pmc sub-runs (~15 s each)")
+                    help="--full: quote roofline.traffic from the committed PMC summary instead of measuring it in two rocprofv3 --pmc sub-runs (~15 s each)")
     ap.add_argument("--audio-lora-r", type=int, default=0,
                     help="train rank-r LoRA on the encoder's q_proj/k_proj too (the reference's release recipe, "
                          "audio_model_lora_config.r = 8); 0 = frozen towers, the BASELINE.json configuration")
@@ -712,6 +746,9 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    full = args.full
+    # HIP events on the GEMM launches: the roofline of --full, or the per-shape tables a probe asks for
+    use_prof = not args.no_prof and bool(full or args.gemm_table or args.gemm_raw)
     # the warm-up steps double as the schedule tuner's trial steps (1 throw-away + 2 per candidate when there are >= 5; with fewer
     # the tuner simply finishes during the first timed steps - it only reads event timers)
     tune = args.autotune and _opt_get(args.opt, 11, -1) < 0 and _opt_get(args.opt, 13, -1) < 0 and B >= 2 and not args.audio_lora_r
@@ -725,12 +762,12 @@ def main():
         _lib.lib().uvx_set_option(15, args.probe_skip)
     barrier()
     prof = (C.c_double * 12)()
-    if not args.no_prof:
+    if use_prof:
         _lib.lib().uvx_prof_begin()
     t0 = time.perf_counter()
     profiled_steps = 0
     for i in range(args.steps):
-        if not args.no_prof:   # the GEMM launches of every N-th timed step carry HIP events (a timed dispatch costs ~1.4 us: profiles/r03_prof_event_overhead.txt)
+        if use_prof:           # the GEMM launches of every N-th timed step carry HIP events (a timed dispatch costs ~1.4 us: profiles/r03_prof_event_overhead.txt)
             on = i % max(1, args.prof_every) == 0
             _lib.lib().uvx_prof_enable(int(on))
             profiled_steps += int(on)
@@ -739,7 +776,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     shapes = None
-    if not args.no_prof:
+    if use_prof:
         if (args.gemm_table or args.gemm_raw) and rank == 0:
             buf = (C.c_double * (6 * 20000))()
             n = _lib.lib().uvx_prof_records(buf, 20000)
@@ -755,6 +792,9 @@ def main():
             shapes = sorted(((k, c, ms) for k, (c, ms) in agg.items()), key=lambda t: -t[2])
         gemm_union_ms = float(_lib.lib().uvx_prof_union_ms(0))      # wall time with >= 1 GEMM executing (= the sum on one stream)
         _lib.check(_lib.lib().uvx_prof_end(prof, 3), "uvx_prof_end")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, **{"param." + k: v for k, v in model.projector_state_dict().items()},
+                                         **{"grad." + k: v for k, v in model.projector_grads().items()}})
     loss_val = float(loss.item())
     # per-rank diagnostics for the scaling runs: every rank's own wall time over the timed region and the time its compute
     # stream waited for the (overlapped) gradient all-reduce - so that a poor 1 -> N line can be read (a slow rank? an exposed
@@ -816,8 +856,9 @@ def main():
                                 + " all-reduce(sum) of one flat f32 bucket, "
                                 f"{trainer.model.proj_grad.numel() * 4 / 1e6:.0f} MB"),
         }
-        out["parity"] = parity_record(args.workload)
-        if not args.no_prof and prof[0] > 0:
+        if full:
+            out["parity"] = parity_record(args.workload)
+        if use_prof and prof[0] > 0:
             # denominator: the union of the GEMM launches' event intervals.  On one stream that is the sum of their durations;
             # with the two-stream LLM schedule launches of the two chains overlap (each interval then includes time the
             # kernel shared the chip), and the union is the time the GEMM family as a whole had the matrix cores.
@@ -828,7 +869,7 @@ def main():
             traffic, traffic_source, traffic_detail = None, None, None
             if args.workload == "c2":
                 plain = args.loss == "ce" and not args.audio_lora_r and not args.opt and not args.gemm_override and world == 1
-                if plain and not args.no_live_traffic and not args.no_cpu_baseline:      # (the probes' A/B arms pass --no-cpu-baseline: no sub-runs there)
+                if full and plain and not args.no_live_traffic and not args.no_cpu_baseline:      # (the probes' A/B arms pass --no-cpu-baseline: no sub-runs there)
                     torch.cuda.synchronize()
                     torch.cuda.empty_cache()          # the sub-runs build their own model next to this process's: hand back every cached block first
                     traffic, traffic_detail = measure_traffic_live(["--workload", "c2"])
@@ -848,7 +889,7 @@ def main():
                                "profiled_steps": f"{profiled_steps} of the {args.steps} timed steps (every {max(1, args.prof_every)}th; HIP events attached to every GEMM dispatch of those steps)",
                                "avg_launch_us": gemm_ms / prof[0] * 1e3,
                                "algorithmic_gflop_per_launch": prof[2] / prof[0] / 1e9}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # The oracle on THIS box's host cores.  Preferred: ONE WHOLE B = 1 step (all layers, nothing extrapolated; ~15 s of
             # CPU work + ~15 s of weight set-up) - needs ~45 GB of host memory for the f32 weights of an 8B-parameter LLM.
             # Otherwise the bounded sample (2 encoder layers + 1 LLM layer timed, scaled to full depth).

@@ -994,6 +994,175 @@ def real_tower_cases():
     print("real_tower_reference:", {k: v["loss"] for k, v in meta["model_cases"].items()}, list(meta["encoder_cases"]))
 
 
+# ---- the differential tests of tests/test_processing_live_reference.py and test_oracle_pinning.py::test_projector_against_live_reference:
+# hypothesis draws the cases (same strategies and example counts as those tests had when they imported the reference), the REFERENCE's
+# outputs are recorded for each, and the tests replay them against the mirror.  Large tensors are recorded by construction, not value:
+# the processor's audio_values as (item, frame offset) chunks of the HF WhisperFeatureExtractor output the reference chunks
+# (asserted here to rebuild the reference's tensor bit for bit), the collator's as their padded shape.
+LIVE_LENGTHS = [0, 1, 159, 160, 161, 319, 320, 321, 4000, 16000, 16001, 47999, 479840, 480000, 480001, 480160, 560000, 960000, 960001]
+LIVE_WORDS = ["Transcribe", "this", "please", "and", "then", "answer", ":", "ok", "\n", "what", "follows", "?"]
+
+
+def _tensor_record(v):
+    t = torch.as_tensor(v)
+    return {"dtype": str(t.dtype), "shape": list(t.shape), "values": t.tolist()}
+
+
+def _live_processor_case(lengths, words, placeholder_delta, chunks, seed):
+    tok = FakeTokenizer()
+    ref = _reference_processor(tok)
+    rng = np.random.RandomState(seed)
+    audios = [rng.randn(n).astype(np.float32) * 0.1 for n in lengths]
+    n_ph = max(0, len(audios) + placeholder_delta)
+    text = " <|audio|> ".join(" ".join(words[i::n_ph + 1]) or "x" for i in range(n_ph + 1))
+    kw = dict(audios=audios, sampling_rate=16000, include_audio_num_chunks=chunks) if audios else {}
+    rec = {"lengths": lengths, "words": words, "placeholder_delta": placeholder_delta, "chunks": chunks, "seed": seed}
+    try:
+        want = ref(text, **kw)
+    except ValueError as e:
+        return {**rec, "error": str(e)}
+    rec["want"] = {}
+    for k in want.keys():
+        if k != "audio_values":
+            rec["want"][k] = _tensor_record(want[k])
+            continue
+        hop = 160
+        feats = transformers.WhisperFeatureExtractor()([np.pad(a, (0, 2 * hop - len(a))) if len(a) < 2 * hop else a for a in audios],
+                                                      sampling_rate=16000, padding="longest", pad_to_multiple_of=hop, truncation=False,
+                                                      return_attention_mask=True)
+        hf, lens = torch.as_tensor(feats.input_features), torch.as_tensor(feats.attention_mask).sum(-1)
+        w = torch.as_tensor(want[k])
+        table = [[i, off] for i in range(len(audios)) for off in range(0, int(lens[i]), 3000)]
+        rebuilt = torch.stack([torch.nn.functional.pad(hf[i, :, off:off + 3000], (0, w.shape[-1] - hf[i, :, off:off + 3000].shape[-1]))
+                               for i, off in table])
+        assert rebuilt.dtype == w.dtype and torch.equal(rebuilt, w), (lengths, chunks)
+        rec["want"][k] = {"dtype": str(w.dtype), "shape": list(w.shape), "chunks": table}
+    return rec
+
+
+def _live_dataproc_case(n_samples, mask, alt, max_resp, inference, system, words, reply, transcript, tail):
+    from fake_tokenizer import FakeChatTokenizer
+    from ultravox.model import ultravox_data_proc
+    user = " ".join(words) + (" <|audio|>" if n_samples is not None else "") + (" thanks" if tail else "")
+    messages = ([{"role": "system", "content": "Be brief ."}] if system else []) + \
+        [{"role": "user", "content": user}, {"role": "assistant", "content": " ".join(reply)}]
+    audio = None if n_samples is None else np.random.RandomState(1).randn(n_samples).astype(np.float32) * 0.1
+    kw = dict(inference_mode=inference, include_alt_fields=alt, max_response_tokens=max_resp)
+    rec = {"n_samples": n_samples, "mask": mask, "system": system, "words": words, "reply": reply, "transcript": transcript, "tail": tail, **kw}
+    tok = FakeChatTokenizer("right")
+    dp = ultravox_data_proc.UltravoxDataproc([], _reference_processor(tok), ultravox_config.LossMaskType(mask), **kw)
+    try:
+        want = dp._process(types.SimpleNamespace(messages=[dict(m) for m in messages], audio=audio, sample_rate=16000,
+                                                 audio_transcript=transcript))
+    except (ValueError, IndexError) as e:
+        return {**rec, "error": [type(e).__name__, str(e)]}
+    rec["want"] = {k: ({"shape": list(v.shape)} if k == "audio_values" else {"value": tolist(v)}) for k, v in want.items()}
+    return rec
+
+
+def _live_collator_case(side, alt, picks):
+    import unittest.mock as mock
+    import torch.nn.functional as F
+    from fake_tokenizer import FakeChatTokenizer
+    from ultravox_amd.config import LossMaskType
+    from ultravox_amd.data_proc import UltravoxDataproc
+    from ultravox_amd.processing import UltravoxProcessor
+    from oracle.reference_cpu import FeatureExtractorRef
+    tok = FakeChatTokenizer(side)
+    tok.pad_token_id = tok.eos_token_id
+    dp = UltravoxDataproc([], UltravoxProcessor(FeatureExtractorRef(80), tokenizer=tok), LossMaskType.LAST_ASSISTANT, include_alt_fields=alt)
+    rng = np.random.RandomState(0)
+    bank = {
+        "asr": ([{"role": "user", "content": "Transcribe <|audio|>"}, {"role": "assistant", "content": "a b c"}], 16000, "a b c"),
+        "qa": ([{"role": "user", "content": "Listen <|audio|> and answer now please"}, {"role": "assistant", "content": "ok then"}], 40000, "hm"),
+        "long": ([{"role": "user", "content": "<|audio|>"}, {"role": "assistant", "content": "long one indeed yes"}], 500000, "x y"),
+        "two": ([{"role": "system", "content": "sys"}, {"role": "user", "content": "A <|audio|> B"}, {"role": "assistant", "content": "r"}], 8000, None),
+    }
+    feats = []
+    for name in picks:
+        msgs, n, tr = bank[name]
+        feats.append(dp._process(types.SimpleNamespace(messages=[dict(m) for m in msgs], audio=rng.randn(n).astype(np.float32) * 0.1,
+                                                       sample_rate=16000, audio_transcript=tr)))
+
+    def hf_pad(features):
+        n = max(len(f["input_ids"]) for f in features)
+
+        def pad(x, v):
+            g = n - len(x)
+            return F.pad(torch.as_tensor(x), (g, 0) if side == "left" else (0, g), value=v)
+        b = {"input_ids": torch.stack([pad(f["input_ids"], tok.pad_token_id) for f in features]),
+             "attention_mask": torch.stack([pad(f["attention_mask"], 0) for f in features]),
+             "labels": torch.stack([pad(f["labels"], -100) for f in features])}
+        if "audio_batch_size" in features[0]:
+            b["audio_batch_size"] = torch.stack([f["audio_batch_size"] for f in features])
+        return b
+    ref = ultravox_processing.DataCollatorForSeq2SeqWithAudio.__new__(ultravox_processing.DataCollatorForSeq2SeqWithAudio)
+    ref.tokenizer, ref.include_alt_fields = tok, alt
+    clone = lambda fs: [{k: (v.clone() if hasattr(v, "clone") else list(v) if isinstance(v, list) else v) for k, v in f.items()} for f in fs]
+    with mock.patch.object(transformers.DataCollatorForSeq2Seq, "__call__", lambda self, features, *a, **k: hf_pad(features)):
+        want = ref(clone(feats))
+    audio = [x for f in feats for x in f.get("audio_values", [])]
+    rebuilt = torch.stack([F.pad(x, (0, want["audio_values"].shape[-1] - x.shape[-1])) for x in audio])
+    assert torch.equal(rebuilt, want["audio_values"])
+    return {"side": side, "alt": alt, "picks": picks,
+            "want": {k: ({"dtype": str(v.dtype), "shape": list(v.shape)} if k == "audio_values" else _tensor_record(v)) for k, v in want.items()}}
+
+
+def live_reference_cases():
+    from hypothesis import HealthCheck, given, settings
+    from hypothesis import strategies as st
+    out = {"processor": [], "dataproc": [], "collator": []}
+
+    @settings(max_examples=30, deadline=None, derandomize=True, database=None, suppress_health_check=[HealthCheck.too_slow])
+    @given(lengths=st.lists(st.sampled_from(LIVE_LENGTHS), max_size=3), words=st.lists(st.sampled_from(LIVE_WORDS), min_size=1, max_size=8),
+           placeholder_delta=st.sampled_from([0, 0, 0, 0, -1, 1]), chunks=st.booleans(), seed=st.integers(0, 3))
+    def processor(lengths, words, placeholder_delta, chunks, seed):
+        out["processor"].append(_live_processor_case(lengths, words, placeholder_delta, chunks, seed))
+
+    @settings(max_examples=40, deadline=None, derandomize=True, database=None, suppress_health_check=[HealthCheck.too_slow])
+    @given(n_samples=st.sampled_from([None, 0, 200, 16000, 40000, 560000]), mask=st.sampled_from(["last_assistant", "after_audio", "all"]),
+           alt=st.booleans(), max_resp=st.sampled_from([None, 1, 3, 50]), inference=st.booleans(), system=st.booleans(),
+           words=st.lists(st.sampled_from(LIVE_WORDS), min_size=1, max_size=6), reply=st.lists(st.sampled_from(LIVE_WORDS), min_size=1, max_size=6),
+           transcript=st.sampled_from([None, "", "hello there", "a b c d e f g"]), tail=st.booleans())
+    def dataproc(**kw):
+        out["dataproc"].append(_live_dataproc_case(**kw))
+
+    @settings(max_examples=25, deadline=None, derandomize=True, database=None, suppress_health_check=[HealthCheck.too_slow])
+    @given(side=st.sampled_from(["right", "left"]), alt=st.booleans(),
+           picks=st.lists(st.sampled_from(["asr", "qa", "long", "two"]), min_size=1, max_size=4))
+    def collator(side, alt, picks):
+        out["collator"].append(_live_collator_case(side, alt, picks))
+
+    import ultravox
+    stub = types.ModuleType("ultravox.data")      # the real package imports librosa / soundfile; only these names are used
+    stub.Dataproc = type("Dataproc", (), {"__init__": lambda self, dataset: setattr(self, "_dataset", dataset)})
+    stub.SizedIterableDataset = stub.VoiceSample = stub.Augmentation = object
+    sys.modules["ultravox.data"] = ultravox.data = stub
+    processor()
+    dataproc()
+    collator()
+    with open(os.path.join(HERE, "live_reference.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("live_reference.json", {k: len(v) for k, v in out.items()})
+
+
+def projector_live_cases():
+    rcfg = ultravox_config.UltravoxConfig(
+        audio_config={"model_type": "whisper", "d_model": 64, "encoder_layers": 1, "encoder_attention_heads": 2,
+                      "encoder_ffn_dim": 64}, text_config={"model_type": "llama", "hidden_size": 128,
+                                                           "intermediate_size": 64, "num_hidden_layers": 1,
+                                                           "num_attention_heads": 2, "vocab_size": 64},
+        hidden_size=128, projector_ln_mid=True)
+    torch.manual_seed(3)
+    proj = ultravox_model.UltravoxProjector(rcfg).float()
+    x = torch.randn(2, 19, 64)
+    with torch.no_grad():
+        y = proj(x)
+    np.savez_compressed(os.path.join(HERE, "projector_live_reference.npz"), x=x.numpy(), y=y.numpy(),
+                        **{"w." + k: v.numpy() for k, v in proj.state_dict().items()})
+    print("projector_live_reference.npz", list(proj.state_dict()))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:          # python make_golden.py kl_lora_forward_cases ...: only the named generators
         for name in sys.argv[1:]:
@@ -1018,3 +1187,5 @@ if __name__ == "__main__":
     kl_cases()
     diff_state_dict_cases()
     dataproc_cases()
+    live_reference_cases()
+    projector_live_cases()

@@ -144,3 +144,26 @@ def test_live_traffic_measurement_parses_the_counter_csv_and_never_raises(tmp_pa
     monkeypatch.setattr(shutil, "which", lambda name: str(fake))
     got, why = bench.measure_traffic_live(["--workload", "c2"], timeout_s=20)
     assert got is None and "sub-run failed" in why
+
+
+def test_dump_outputs_writes_float_arrays_within_budget_and_samples_the_same_positions(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one DIR/<name>.npy per array, float32 (integer outputs as exact float64), small arrays whole,
+    larger ones as a fixed sample (the same positions in every run), DUMP_MAX_BYTES of data at most in all."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 4096)
+    big = torch.arange(100000, dtype=torch.bfloat16).reshape(100, 1000)
+    arrays = {"loss": torch.tensor(2.5), "param.w": big, "grad.w": torch.randn(7, 3), "tokens": torch.tensor([[1, 2 ** 40]])}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and got["loss"] == 2.5
+    assert got["grad.w"].dtype == np.float32 and np.array_equal(got["grad.w"], arrays["grad.w"].numpy())
+    assert got["tokens"].dtype == np.float64 and got["tokens"].tolist() == [[1.0, 2.0 ** 40]]
+    w = got["param.w"]
+    assert w.dtype == np.float32 and w.shape == (1024,) and np.all(np.diff(w) >= 0)          # a sorted sample of the flat array
+    assert np.array_equal(w, big.reshape(-1)[torch.from_numpy(np.sort(np.random.default_rng(0).choice(100000, 1024, replace=False)))].float().numpy())
+    assert sum(g.nbytes for g in got.values()) <= bench.DUMP_MAX_BYTES
+    for n in arrays:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n])
