@@ -97,6 +97,9 @@ __global__ void ce_rows_k(const T* __restrict__ logits, const int64_t* __restric
     }
     return;
   }
+  // the target logit is read before the block reductions: with dlogits == logits another wave may overwrite it as soon as the
+  // reductions are done
+  const float x_tgt = threadIdx.x == 0 ? ldf<T>(lr + tgt) : 0.f;
   // online max / sum-exp, per thread then block
   float m = -__builtin_huge_valf(), s = 0.f;
   for (int c = threadIdx.x * 8; c < V; c += blockDim.x * 8) {
@@ -116,7 +119,7 @@ __global__ void ce_rows_k(const T* __restrict__ logits, const int64_t* __restric
   const float S = block_sum(s * expf(m - M), red);
   const float lse = M + logf(S);
   const float n_valid = scratch[0];
-  if (threadIdx.x == 0) row_loss[lrow] = lse - ldf<T>(lr + tgt);
+  if (threadIdx.x == 0) row_loss[lrow] = lse - x_tgt;
   if (dr) {
     const float g = grad_scale / n_valid;
     for (int c = threadIdx.x * 8; c < V; c += blockDim.x * 8) {

@@ -302,7 +302,8 @@ __global__ void rmsnorm_fwd_reg_k(const T* __restrict__ x, const T* __restrict__
 // One block handles `rpb` consecutive rows; each thread owns fixed columns so the weight gradient
 // is accumulated in registers and flushed once per column per block: into dw_part [block][cols] when the caller lends that scratch
 // (round 6: rmsnorm_dw_reduce_k then sums the blocks in block order - the projector's norm-weight gradients were the one output of a
-// training step that moved by an ulp from run to run), else with an atomicAdd into dw (uvx_rmsnorm_bwd: the ABI has no scratch argument).
+// training step that moved by an ulp from run to run), else with an atomicAdd into dw from a single block (uvx_rmsnorm_bwd: the ABI has
+// no scratch argument).
 // MV: 8-element vectors per thread (static trip count; the launcher picks the smallest that covers the row - at the LLM's 4096
 // columns MV = 2 needs half the registers of MV = 6 and twice as many rows are in flight per CU)
 template <typename T, bool WANT_DX, bool WANT_DW, int MV>
@@ -494,7 +495,9 @@ static int rms_bwd_launch(hipStream_t st, const void* dy, const void* x, const v
   const int th = 256;   // (512 threads with one vector each: 20.4 vs 17.7 us at 2528 x 4096 - profiles/r03_rmsnorm_bwd_variants.txt)
   UVX_CHECK(cols % 8 == 0 && cols <= th * 8 * MAXV, UVX_ERR_SHAPE, "rmsnorm_bwd: cols=%d unsupported", cols);
   if (rows == 0) return UVX_OK;
-  const int rpb = dw ? 16 : 1;
+  // without dw_part scratch (uvx_rmsnorm_bwd: the ABI has none) the blocks would meet in dw through atomicAdd, whose order - and so
+  // the last bit of dw - changes from run to run: one block then takes every row, the single add per column is deterministic
+  const int rpb = dw ? (dw_part ? 16 : rows) : 1;
   const int grid = (rows + rpb - 1) / rpb;
 #define L(DX, DW)                                                                                                 \
   do {                                                                                                            \
