@@ -10,22 +10,11 @@
 // chunk of tokens on top of a filled cache (conversation turns) goes through uvx_llm_prefill_chunk.
 // KV cache layout: [layer][k | v][B][Tmax][kv_heads * head_dim], caller-owned.
 #include <algorithm>
-#include "common.h"
-#include "kernels.h"
+#include "host_util.h"
 #include "../../include/uvx.h"
 
 namespace {
 using namespace uvx;
-
-struct Arena {
-  char* base; size_t cap; size_t off = 0;
-  Arena(void* b, size_t c) : base((char*)b), cap(c) {}
-  void* take(size_t bytes) { const size_t a = (off + 255) & ~(size_t)255; off = a + bytes; return base ? (void*)(base + a) : nullptr; }
-  bool fits() const { return !base || off <= cap; }
-};
-inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }
-inline char* at(const void* p, size_t elems, int dtype) { return (char*)p + elems * esz(dtype); }
-#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 struct InferWs {
   void *x, *x2, *n, *qkv, *vt, *o, *gu, *act, *last, *hn;
@@ -36,7 +25,7 @@ struct InferWs {
 InferWs carve(Arena& a, const uvx_config_t& c, int B, int T) {
   InferWs w;
   const size_t es = esz(c.dtype), M = (size_t)B * T;
-  w.M = B * T; w.Tp = (T + 63) / 64 * 64;
+  w.M = B * T; w.Tp = rup(T, 64);
   w.QKV = (c.llm_heads + 2 * c.llm_kv_heads) * c.llm_head_dim; w.OD = c.llm_heads * c.llm_head_dim;
   w.x = a.take(M * c.llm_d * es); w.x2 = a.take(M * c.llm_d * es); w.n = a.take(M * c.llm_d * es);
   w.qkv = a.take(M * w.QKV * es);
@@ -433,12 +422,6 @@ __global__ void greedy_select_k(const T* __restrict__ logits, int V, const int64
 float gemma_normalizer(const uvx_config_t& c) {
   const float n = sqrtf((float)c.llm_d);
   return c.dtype == DT_BF16 ? bf2f(f2bf(n)) : n;
-}
-
-GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) {
-  GemmDesc g;
-  g.A = A; g.B = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
-  return g;
 }
 
 // one decoder layer on M = B*T rows; attention supplied by the caller

@@ -1,0 +1,47 @@
+// Host-side helpers of the orchestration files (model.hip, generate.hip, wav2vec2.hip, enc_stack.hip): workspace carving, element
+// addressing, error propagation, the plain linear's GEMM descriptor.
+#pragma once
+#include "common.h"
+#include "kernels.h"
+
+namespace uvx {
+
+// Bump allocator over the caller's workspace (256-byte aligned slices).  base == NULL: a dry run that only measures.
+struct Arena {
+  char* base;
+  size_t cap;
+  size_t off = 0;
+  Arena(void* b, size_t c) : base((char*)b), cap(c) {}
+  void* take(size_t bytes) {
+    const size_t a = (off + 255) & ~(size_t)255;
+    off = a + bytes;
+    return base ? (void*)(base + a) : nullptr;
+  }
+  bool fits() const { return !base || off <= cap; }
+};
+
+inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }
+inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+inline char* at(const void* p, size_t elems, int dtype) { return (char*)p + elems * esz(dtype); }
+
+#define RC(expr)            \
+  do {                      \
+    int _rc = (expr);       \
+    if (_rc) return _rc;    \
+  } while (0)
+
+// y [M, N] = x [M, K] . W [N, K]^T
+inline GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) {
+  GemmDesc g;
+  g.A = A; g.B = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
+  return g;
+}
+
+// Timing probe (tuning option 15, default 0): bit mask of kernel classes NOT launched - the step's results are then garbage, its
+// time says what that class costs inside the overlapped schedule (bench.py --opt 15=<mask>; never set by the product).
+// 1 LLM attention backward, 2 LLM attention forward, 4 SwiGLU backward, 8 RMSNorm backward, 16 RMSNorm forward, 32 RoPE forward,
+// 64 attention forward of either audio tower's layer stack, 128 every LayerNorm forward inside that stack (enc_stack.hip: the layers' norms in
+// the forward walks and their recomputes in the backward; not the towers' final LayerNorm)
+inline bool probe_skip(int bit) { return (g_options[15] & bit) != 0; }
+
+}  // namespace uvx

@@ -4,36 +4,13 @@
 #include <type_traits>
 #include <unordered_map>
 #include <algorithm>
-#include "common.h"
-#include "kernels.h"
+#include "host_util.h"
+#include "enc_stack.h"
 #include "../../include/uvx.h"
 
 namespace {
 
 using namespace uvx;
-
-struct Arena {
-  char* base;
-  size_t cap;
-  size_t off = 0;
-  Arena(void* b, size_t c) : base((char*)b), cap(c) {}
-  void* take(size_t bytes) {
-    const size_t a = (off + 255) & ~(size_t)255;
-    off = a + bytes;
-    return base ? (void*)(base + a) : nullptr;
-  }
-  bool fits() const { return !base || off <= cap; }
-};
-
-inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline char* at(const void* p, size_t elems, int dtype) { return (char*)p + elems * esz(dtype); }
-
-#define RC(expr)            \
-  do {                      \
-    int _rc = (expr);       \
-    if (_rc) return _rc;    \
-  } while (0)
 
 __global__ void enc_kvlen_k(const int64_t* __restrict__ audio_lens, int32_t* __restrict__ kv_len, int B, int Te) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,81 +42,30 @@ __global__ void full_range_k(int32_t* __restrict__ kv_start, int32_t* __restrict
 }
 
 // ------------------------------------------------------------------ encoder
-// per-layer stash of the LoRA-training forward (uvx_encoder_fwd_train -> uvx_encoder_bwd)
-struct EncLayerStash {
-  void *x_in, *qkv, *o, *x_mid, *pre, *t;   // t = [lora_A_q(n) | lora_A_k(n)], [M, 128] (columns 0..r-1 and 64..64+r-1)
-  float* lse;
-  void *bqT, *bkT;                           // lora_B^T [r, d] of this layer: every rank-r product reads rows
-  void *t2, *bvT, *boT;                      // v_proj / out_proj adapters (ABI 17): t2 = [lora_A_v(n) | lora_A_o(attention output)] [M, 128]
-  void* t3;                                  // fc1 / fc2 adapters (ABI 18): [lora_A_fc1(n2) | lora_A_fc2(gelu(fc1))] [M, 128]
-};
+// the conv stem's buffers in front of the shared layer stack's (enc_stack.h)
 struct EncWs {
-  void *im2col, *c1, *x, *n, *qkv, *vt, *o, *f;
-  int32_t* kvlen;
-  int Te, Tp, M, Kp1;
-  void* sk; size_t sk_bytes;    // inference at one or two clips: split-K scratch of the layer GEMMs (gemm.hip "Split-K"), else null
-  // training only
-  char* slots; size_t slot_bytes; EncLayerStash ls0;
-  void *dx, *d_n, *d_o, *d_f, *d_qkv, *qT, *kT, *doT, *u, *u2;   // u2: [d v . B_v | d x_mid . B_o] [M, 128]
-  void *u3, *lbT;   // u3: [d pre . B_fc1 | d x_out . B_fc2] [M, 128]; lbT: one MLP adapter's lora_B^T [r, max(d, ffn)] (transposed again in the backward)
-  float *delta, *wg;   // wg: lora_wgrad scratch
-  int Mp;
+  void *im2col, *c1;
+  int Kp1;
+  EncStackWs t;
 };
-void enc_slot(Arena& a, const uvx_config_t& c, int B, int Te, EncLayerStash& s) {
-  const size_t es = esz(c.dtype), M = (size_t)B * Te, d = c.enc_d;
-  s.x_in = a.take(M * d * es); s.qkv = a.take(M * 3 * d * es); s.o = a.take(M * d * es); s.x_mid = a.take(M * d * es);
-  s.pre = a.take(M * c.enc_ffn * es); s.t = a.take(M * 128 * es);
-  s.lse = (float*)a.take(sizeof(float) * (size_t)B * c.enc_heads * Te);
-  s.bqT = a.take(64 * d * es); s.bkT = a.take(64 * d * es);
-  s.t2 = a.take(M * 128 * es); s.bvT = a.take(64 * d * es); s.boT = a.take(64 * d * es);
-  s.t3 = a.take(M * 128 * es);
+// what the Whisper tower asks of the shared stack: pre-LN layers, key padding and the latency mask, every launch form built so far
+EncStackDesc enc_desc(const uvx_config_t& c, int B, int F, bool train) {
+  EncStackDesc D = {};
+  D.dtype = c.dtype; D.d = c.enc_d; D.heads = c.enc_heads; D.ffn = c.enc_ffn; D.layers = c.enc_layers; D.ln_eps = c.ln_eps;
+  D.B = B; D.T = (F - 1) / 2 + 1; D.Tp = rup(D.T, 64);
+  D.train = train; D.post_ln = false; D.key_padding = true; D.block = c.enc_block;
+  // one or two clips (generate() at B = 1, 2): 1500 / 3000 rows are 48 ... 144 of the 128- / 256-wide tiles on 256 CUs
+  D.splitk = !train && c.dtype == DT_BF16 && D.M() > 64 && D.M() <= 3072;
+  D.pair_qk = true; D.fuse_gelu = c.dtype == DT_BF16 && g_options[21] != 1; D.mlp_adapters = true;
+  return D;
 }
-EncLayerStash enc_layer(const EncWs& w, int l) {
-  EncLayerStash s = w.ls0;
-  const size_t off = w.slot_bytes * l;
-  void** ps[] = {&s.x_in, &s.qkv, &s.o, &s.x_mid, &s.pre, &s.t, (void**)&s.lse, &s.bqT, &s.bkT, &s.t2, &s.bvT, &s.boT, &s.t3};
-  for (void** q : ps) if (*q) *q = (char*)*q + off;
-  return s;
-}
-EncWs enc_carve(Arena& a, const uvx_config_t& c, int B, int F, bool train = false) {
+EncWs enc_carve(Arena& a, const uvx_config_t& c, const EncStackDesc& D, int F) {
   EncWs w = {};
   const size_t es = esz(c.dtype);
-  w.Te = (F - 1) / 2 + 1;
-  w.Tp = rup(w.Te, 64);
-  w.M = B * w.Te;
   w.Kp1 = rup(3 * c.n_mels, 64);
-  const int dh = c.enc_d / c.enc_heads;
-  w.im2col = a.take((size_t)B * F * w.Kp1 * es);
-  w.c1 = a.take((size_t)B * (F + 2) * c.enc_d * es);
-  w.x = a.take((size_t)w.M * c.enc_d * es);
-  w.n = a.take((size_t)w.M * c.enc_d * es);
-  w.qkv = a.take((size_t)w.M * 3 * c.enc_d * es);
-  w.vt = a.take((size_t)B * c.enc_heads * dh * w.Tp * es);
-  w.o = a.take((size_t)w.M * c.enc_d * es);
-  w.f = a.take((size_t)w.M * c.enc_ffn * es);
-  w.kvlen = (int32_t*)a.take(sizeof(int32_t) * B);
-  // one or two clips (generate() at B = 1, 2): 1500 / 3000 rows are 48 ... 144 of the 128- / 256-wide tiles on 256 CUs
-  w.sk_bytes = !train && c.dtype == DT_BF16 && w.M > 64 && w.M <= 3072 ? gemm_splitk_ws_bytes(w.M, c.enc_ffn) : 0;
-  w.sk = w.sk_bytes ? a.take(w.sk_bytes) : nullptr;
-  if (train) {
-    const size_t M = (size_t)w.M, d = c.enc_d;
-    w.Mp = rup(w.M, 64);
-    const size_t start = (a.off + 255) & ~(size_t)255;
-    a.off = start;
-    enc_slot(a, c, B, w.Te, w.ls0);
-    a.off = (a.off + 255) & ~(size_t)255;
-    w.slot_bytes = a.off - start;
-    w.slots = a.base ? a.base + start : nullptr;
-    a.off = start + w.slot_bytes * c.enc_layers;
-    w.dx = a.take(M * d * es); w.d_n = a.take(M * d * es); w.d_o = a.take(M * d * es);
-    w.d_f = a.take(M * c.enc_ffn * es); w.d_qkv = a.take(M * 3 * d * es);
-    const size_t ht = (size_t)B * c.enc_heads * dh * w.Tp * es;
-    w.qT = a.take(ht); w.kT = a.take(ht); w.doT = a.take(ht);
-    w.u = a.take(M * 128 * es); w.u2 = a.take(M * 128 * es); w.u3 = a.take(M * 128 * es);
-    w.lbT = a.take((size_t)64 * std::max(c.enc_d, c.enc_ffn) * es);
-    w.delta = (float*)a.take(sizeof(float) * (size_t)B * c.enc_heads * w.Te);
-    w.wg = (float*)a.take(sizeof(float) * (size_t)lora_wgrad_scratch_floats(w.M, std::max(c.enc_d, c.enc_ffn), 64));
-  }
+  w.im2col = a.take((size_t)D.B * F * w.Kp1 * es);
+  w.c1 = a.take((size_t)D.B * (F + 2) * c.enc_d * es);
+  w.t = enc_stack_carve(a, D);
   return w;
 }
 
@@ -319,12 +245,6 @@ int check_pair(const void* ws, bool compact) {
   return UVX_OK;
 }
 
-// Timing probe (tuning option 15, default 0): bit mask of kernel classes NOT launched - the step's results are then garbage, its
-// time says what that class costs inside the overlapped schedule (bench.py --opt 15=<mask>; never set by the product).
-// 1 LLM attention backward, 2 LLM attention forward, 4 SwiGLU backward, 8 RMSNorm backward, 16 RMSNorm forward, 32 RoPE forward,
-// 64 encoder attention, 128 encoder LayerNorm
-inline bool probe_skip(int bit) { return (g_options[15] & bit) != 0; }
-
 // Batch slice [b0, b0 + nb) of the carved LLM workspace: every buffer is batch-major at the top level ([B*T, ld] rows or
 // [B, ...]), so a slice is the same record with its pointers advanced.  Used by the two-stream schedule below.
 LlmWs llm_view(const LlmWs& w, const uvx_config_t& c, int b0, int nb, int T) {
@@ -477,11 +397,6 @@ float gemma_normalizer(const uvx_config_t& c) {
   return c.dtype == DT_BF16 ? bf2f(f2bf(n)) : n;
 }
 
-GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) {
-  GemmDesc g;
-  g.A = A; g.B = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
-  return g;
-}
 // The dgrad of a frozen linear y = x . W^T (W [N_out, N_in]):  d x [M, N_in] = d y [M, N_out] . W.  With the transposed copy Wt [N_in, N_out]
 // it is the NT problem lin(d y, Wt, ..); without one (Wt == NULL; bf16, round 6) the NN form reads W as it lies (GemmDesc::b_kn: B [K, N],
 // row stride N) - bit-identical, and the copy (16 GB of them for Llama-3-8B) need not exist.
@@ -503,11 +418,10 @@ extern "C" int32_t uvx_logmel(void* stream, const float* pcm, const float* windo
 extern "C" size_t uvx_encoder_ws_bytes(const uvx_config_t* cfg, int32_t B, int32_t F) {
   if (!cfg) return 0;
   Arena a(nullptr, 0);
-  enc_carve(a, *cfg, B, F);
+  enc_carve(a, *cfg, enc_desc(*cfg, B, F, false), F);
   return a.off + 256;
 }
 
-static GemmDesc enc_sk(GemmDesc g, const EncWs& s) { g.splitk_ws = s.sk; g.splitk_ws_bytes = s.sk_bytes; return g; }
 static int enc_forward(hipStream_t st, const uvx_config_t& c, const uvx_encoder_weights_t* w, const uvx_encoder_lora_t* lora,
                        const void* mel, int mel_is_f32, const int64_t* audio_lens, int B, int F, void* out, void* workspace,
                        size_t ws_bytes) {
@@ -523,9 +437,10 @@ static int enc_forward(hipStream_t st, const uvx_config_t& c, const uvx_encoder_
     UVX_CHECK(!lora->layers[l].u.a, UVX_ERR_INVALID, "encoder LoRA: layer %d has an up_proj adapter (the Whisper MLP is fc1 / fc2: g / d)", l);
   if (B == 0 || F == 0) return UVX_OK;
   Arena a(workspace, ws_bytes);
-  EncWs s = enc_carve(a, c, B, F, train);
+  EncStackDesc D = enc_desc(c, B, F, train);
+  const EncWs s = enc_carve(a, c, D, F);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "encoder_fwd: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, d = c.enc_d, Te = s.Te, M = s.M, dh = d / c.enc_heads;
+  const int dt = c.dtype, d = c.enc_d, Te = D.T, M = D.M();
   const size_t es = esz(dt);
 
   // conv1 + GELU (ultravox_model.py:893) as im2col + GEMM, written time-major into a buffer with one
@@ -539,94 +454,22 @@ static int enc_forward(hipStream_t st, const uvx_config_t& c, const uvx_encoder_
     g.sA = (long long)F * s.Kp1; g.sC = (long long)(F + 2) * d;
     RC(gemm(st, dt, g));
   }
-  void* x = train ? enc_layer(s, 0).x_in : s.x;   // the running hidden state (training: lives in the layer stashes)
+  void* x = train ? enc_stack_layer(s.t, 0).x_in : s.t.x;   // the running hidden state (training: lives in the layer stashes)
   {  // conv2 + GELU (:894), permute (:896), + embed_positions[:Te] (:897-899)
     GemmDesc g = lin(s.c1, w->conv2_w, x, Te, d, 3 * d);
     g.lda = 2 * d; g.bias = w->conv2_b; g.act = 1; g.batch = B;
     g.sA = (long long)(F + 2) * d; g.sC = (long long)Te * d;
     g.residual = w->pos; g.ldr = d; g.sR = 0;
-    RC(gemm(st, dt, enc_sk(g, s)));
+    g.splitk_ws = s.t.sk; g.splitk_ws_bytes = s.t.sk_bytes;
+    RC(gemm(st, dt, g));
   }
   // key padding mask from audio_len (:915-926)
-  const int32_t* kvlen = nullptr;
   if (audio_lens) {
-    hipLaunchKernelGGL(enc_kvlen_k, dim3(cdiv(B, 64)), dim3(64), 0, st, audio_lens, s.kvlen, B, Te);
+    hipLaunchKernelGGL(enc_kvlen_k, dim3(cdiv(B, 64)), dim3(64), 0, st, audio_lens, s.t.kvlen, B, Te);
     UVX_LAUNCH_CHECK();
-    kvlen = s.kvlen;
+    D.kv_len = s.t.kvlen;
   }
-  const float qscale = 1.0f / sqrtf((float)dh);
-  for (int l = 0; l < c.enc_layers; ++l) {
-    const uvx_enc_layer_t& L = w->layers[l];
-    EncLayerStash S = train ? enc_layer(s, l) : EncLayerStash{};
-    void* qkv = train ? S.qkv : s.qkv;
-    void* o = train ? S.o : s.o;
-    void* x_mid = train ? S.x_mid : x;            // inference: the residual stream is updated in place
-    void* x_out = !train ? x : (l + 1 < c.enc_layers ? enc_layer(s, l + 1).x_in : s.x);
-    if (!probe_skip(128)) RC(layernorm_fwd(st, dt, x, L.ln1_w, L.ln1_b, s.n, M, d, c.ln_eps));
-    {
-      GemmDesc g = lin(s.n, L.wqkv, qkv, M, 3 * d, d);
-      g.bias = L.bqkv;
-      RC(gemm(st, dt, enc_sk(g, s)));
-    }
-    if (train) {
-      // peft LoRA on q_proj / k_proj: result += lora_B(lora_A(x)) * scaling (and q carries Whisper's head_dim^-0.5,
-      // folded into wqkv at pack time).  Rank-r products on the VALU (lora.hip): HBM-bound, no padding to an MFMA tile.
-      // (Round 6, tried and removed: the two up-projections as terms of the q|k|v GEMM's whole-line epilogue - and of its dgrad's - instead
-      //  of read-modify-write passes over qkv / d n.  Bit-identical, 96 launches fewer per step and 0.25 ms per step SLOWER: the terms'
-      //  loads sit in an epilogue nothing overlaps, and their registers cost the 256-row tile its spill-free budget - profiles/r06_flavours.txt.)
-      const uvx_enc_lora_layer_t& R = lora->layers[l];
-      const int r = lora->r;
-      if (R.q.a && R.k.a) {      // the default target_modules: the pair in one launch each
-        RC(lora_transpose2(st, dt, R.q.b, S.bqT, d, R.k.b, S.bkT, d, r));
-        RC(lora_down2(st, dt, s.n, s.n, d, R.q.a, R.k.a, S.t, at(S.t, 64, dt), 128, M, d, r, 1.0f, 1.0f));
-        RC(lora_up2(st, dt, S.t, at(S.t, 64, dt), 128, S.bqT, S.bkT, qkv, at(qkv, d, dt), 3 * d, M, d, d, r, lora->scaling * qscale, lora->scaling));
-      } else {
-        if (R.q.a) RC(lora_apply(st, dt, s.n, d, R.q, S.bqT, S.t, qkv, 3 * d, M, d, d, r, lora->scaling * qscale));
-        if (R.k.a) RC(lora_apply(st, dt, s.n, d, R.k, S.bkT, at(S.t, 64, dt), at(qkv, d, dt), 3 * d, M, d, d, r, lora->scaling));
-      }
-      // v_proj (target_modules beyond the default; ABI 17): the same product into the v columns
-      if (R.v.a) RC(lora_apply(st, dt, s.n, d, R.v, S.bvT, S.t2, at(qkv, 2 * d, dt), 3 * d, M, d, d, r, lora->scaling));
-    }
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(qkv, 2 * d, dt), s.vt, B, Te, s.Tp, c.enc_heads, dh, 3 * d));
-    AttnDesc ad;
-    ad.q = qkv; ad.k = at(qkv, d, dt); ad.v = at(qkv, 2 * d, dt); ad.vt = s.vt; ad.o = o; ad.lse = train ? S.lse : nullptr;
-    ad.kv_len = kvlen; ad.B = B; ad.T = Te; ad.Tp = s.Tp; ad.Hq = c.enc_heads; ad.Hkv = c.enc_heads; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = 3 * d; ad.ldo = d; ad.causal = 0; ad.block = c.enc_block;
-    ad.scale = 1.0f;  // q_proj is pre-scaled by head_dim^-0.5 at pack time (exact in bf16 for dh = 64)
-    if (!probe_skip(64)) RC(attention_fwd(st, dt, ad));
-    {
-      GemmDesc g = lin(o, L.wo, x_mid, M, d, d);
-      g.bias = L.bo; g.residual = x; g.ldr = d;
-      RC(gemm(st, dt, enc_sk(g, s)));
-    }
-    // out_proj adapter: x_mid += lora_B(lora_A(attention output)) * scaling
-    if (train && lora->layers[l].o.a) RC(lora_apply(st, dt, o, d, lora->layers[l].o, S.boT, at(S.t2, 64, dt), x_mid, d, M, d, d, lora->r, lora->scaling));
-    if (!probe_skip(128)) RC(layernorm_fwd(st, dt, x_mid, L.ln2_w, L.ln2_b, s.n, M, d, c.ln_eps));
-    if (train) {   // keep the fc1 pre-activation for the GELU backward
-      GemmDesc g = lin(s.n, L.fc1_w, S.pre, M, c.enc_ffn, d);
-      g.bias = L.fc1_b;
-      // bf16: the GELU runs in the GEMM's epilogue, which writes the pre-activation AND the activation (act 2; tuning option 21 = 1: the
-      // separate gelu_fwd pass of rounds 3-5 - bit-identical)
-      const uvx_lora_proj_t& A1 = lora->layers[l].g;      // fc1 adapter (ABI 18): joins the pre-activation, so the GELU runs after it
-      const bool fused = dt == DT_BF16 && g_options[21] != 1 && !A1.a;
-      if (fused) { g.act = 2; g.C2 = s.f; g.ldc2 = c.enc_ffn; }
-      RC(gemm(st, dt, g));
-      if (A1.a) RC(lora_apply(st, dt, s.n, d, A1, s.lbT, S.t3, S.pre, c.enc_ffn, M, d, c.enc_ffn, lora->r, lora->scaling));
-      if (!fused) RC(gelu_fwd(st, dt, S.pre, s.f, (long long)M * c.enc_ffn));
-    } else {
-      GemmDesc g = lin(s.n, L.fc1_w, s.f, M, c.enc_ffn, d);
-      g.bias = L.fc1_b; g.act = 1;
-      RC(gemm(st, dt, enc_sk(g, s)));
-    }
-    {
-      GemmDesc g = lin(s.f, L.fc2_w, x_out, M, d, c.enc_ffn);
-      g.bias = L.fc2_b; g.residual = x_mid; g.ldr = d;
-      RC(gemm(st, dt, enc_sk(g, s)));
-    }
-    if (train && lora->layers[l].d.a)      // fc2 adapter
-      RC(lora_apply(st, dt, s.f, c.enc_ffn, lora->layers[l].d, s.lbT, at(S.t3, 64, dt), x_out, d, M, c.enc_ffn, d, lora->r, lora->scaling));
-    x = x_out;
-  }
+  RC(enc_stack_fwd_pre_ln(st, D, s.t, w->layers, lora, x));
   RC(layernorm_fwd(st, dt, x, w->lnf_w, w->lnf_b, out, M, d, c.ln_eps));  // :980
   return UVX_OK;
 }
@@ -642,7 +485,7 @@ extern "C" int32_t uvx_encoder_fwd(void* stream, const uvx_config_t* cfg, const 
 extern "C" size_t uvx_encoder_train_ws_bytes(const uvx_config_t* cfg, int32_t B, int32_t F) {
   if (!cfg) return 0;
   Arena a(nullptr, 0);
-  enc_carve(a, *cfg, B, F, true);
+  enc_carve(a, *cfg, enc_desc(*cfg, B, F, true), F);
   return a.off + 256;
 }
 
@@ -667,94 +510,14 @@ extern "C" int32_t uvx_encoder_bwd(void* stream, const uvx_config_t* cfg, const 
   hipStream_t st = (hipStream_t)stream;
   if (B == 0 || F == 0) return UVX_OK;
   Arena a(workspace, ws_bytes);
-  EncWs s = enc_carve(a, c, B, F, true);
+  EncStackDesc D = enc_desc(c, B, F, true);
+  D.who = "encoder_bwd";
+  const EncWs s = enc_carve(a, c, D, F);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "encoder_bwd: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, d = c.enc_d, Te = s.Te, M = s.M, dh = d / c.enc_heads, r = lora->r;
-  const float qscale = 1.0f / sqrtf((float)dh);
-  // ln_post backward: out = LN(x_final); x_final is the running state after the last layer (s.x)
-  RC(layernorm_bwd(st, dt, d_out, s.x, w->lnf_w, nullptr, s.dx, M, d, c.ln_eps));
-  for (int l = c.enc_layers - 1; l >= 0; --l) {
-    const uvx_enc_layer_t& L = w->layers[l];
-    UVX_CHECK(L.wqkv_t && L.wo_t && L.fc1_t && L.fc2_t, UVX_ERR_INVALID, "encoder_bwd: layer %d lacks transposed weights", l);
-    EncLayerStash S = enc_layer(s, l);
-    // ---- MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid)))) ----
-    {  // d f = (d x . W_fc2) * gelu'(pre): bf16 - in the dgrad GEMM's epilogue (act 3; option 21 = 1: the separate gelu_bwd pass, bit-identical)
-      const uvx_enc_lora_layer_t& Rm = lora->layers[l];
-      const uvx_enc_lora_layer_grads_t& Gm = grads->layers[l];
-      const long long wgf = lora_wgrad_scratch_floats(s.M, std::max(c.enc_d, c.enc_ffn), 64);
-      GemmDesc g = lin(s.dx, L.fc2_t, s.d_f, M, c.enc_ffn, d);
-      const bool fused = dt == DT_BF16 && g_options[21] != 1 && !Rm.d.a;
-      if (fused) { g.act = 3; g.C2 = S.pre; g.ldc2 = c.enc_ffn; }
-      RC(gemm(st, dt, g));
-      if (Rm.d.a) {      // fc2 adapter: its input gelu(pre) is recomputed; d f += (d x . B * scaling) . A BEFORE the GELU backward
-        RC(gelu_fwd(st, dt, S.pre, s.f, (long long)M * c.enc_ffn));
-        RC(lora_transpose(st, dt, Rm.d.b, s.lbT, d, r));
-        RC(lora_apply_bwd(st, dt, s.f, c.enc_ffn, s.dx, d, s.lbT, at(S.t3, 64, dt), at(s.u3, 64, dt), Gm.d, M, c.enc_ffn, d, r, lora->scaling, s.wg, wgf));
-        RC(lora_up(st, dt, at(s.u3, 64, dt), 128, Rm.d.a, 1, s.d_f, c.enc_ffn, M, c.enc_ffn, r, 1.0f, 1));
-      }
-      if (!fused) RC(gelu_bwd(st, dt, s.d_f, S.pre, s.d_f, (long long)M * c.enc_ffn));
-    }
-    RC(gemm(st, dt, lin(s.d_f, L.fc1_t, s.d_n, M, d, c.enc_ffn)));
-    if (lora->layers[l].g.a) {      // fc1 adapter: its input LN2(x_mid) is recomputed; d n2 += (d pre . B * scaling) . A
-      const long long wgf = lora_wgrad_scratch_floats(s.M, std::max(c.enc_d, c.enc_ffn), 64);
-      RC(layernorm_fwd(st, dt, S.x_mid, L.ln2_w, L.ln2_b, s.n, M, d, c.ln_eps));
-      RC(lora_transpose(st, dt, lora->layers[l].g.b, s.lbT, c.enc_ffn, r));
-      RC(lora_apply_bwd(st, dt, s.n, d, s.d_f, c.enc_ffn, s.lbT, S.t3, s.u3, grads->layers[l].g, M, d, c.enc_ffn, r, lora->scaling, s.wg, wgf));
-      RC(lora_up(st, dt, s.u3, 128, lora->layers[l].g.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    }
-    RC(layernorm_bwd(st, dt, s.d_n, S.x_mid, L.ln2_w, s.dx, s.dx, M, d, c.ln_eps));
-    // ---- attention: x_mid = x_in + wo(attn(q, k, v)) ----
-    RC(gemm(st, dt, lin(s.dx, L.wo_t, s.d_o, M, d, d)));
-    const uvx_enc_lora_layer_t& R = lora->layers[l];
-    const uvx_enc_lora_layer_grads_t& G = grads->layers[l];
-    const long long wg_floats = lora_wgrad_scratch_floats(s.M, std::max(c.enc_d, c.enc_ffn), 64);
-    if (R.o.a) {   // out_proj adapter: its gradients, and d o += (d x_mid . B_o * scaling) . A_o
-      RC(lora_apply_bwd(st, dt, S.o, d, s.dx, d, S.boT, at(S.t2, 64, dt), at(s.u2, 64, dt), G.o, M, d, d, r, lora->scaling, s.wg, wg_floats));
-      RC(lora_up(st, dt, at(s.u2, 64, dt), 128, R.o.a, 1, s.d_o, d, M, d, r, 1.0f, 1));
-    }
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, S.qkv, s.qT, B, Te, s.Tp, c.enc_heads, dh, 3 * d));
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(S.qkv, d, dt), s.kT, B, Te, s.Tp, c.enc_heads, dh, 3 * d));
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, s.d_o, s.doT, B, Te, s.Tp, c.enc_heads, dh, d));
-    AttnBwdDesc bd;
-    AttnDesc& ad = bd.f;
-    ad.q = S.qkv; ad.k = at(S.qkv, d, dt); ad.v = at(S.qkv, 2 * d, dt); ad.o = S.o; ad.lse = S.lse;
-    ad.kv_len = audio_lens ? s.kvlen : nullptr;          // written by the forward pass (same audio_lens)
-    ad.B = B; ad.T = Te; ad.Tp = s.Tp; ad.Hq = c.enc_heads; ad.Hkv = c.enc_heads; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = 3 * d; ad.ldo = d; ad.causal = 0; ad.block = c.enc_block; ad.scale = 1.0f;
-    bd.dout = s.d_o; bd.qt = s.qT; bd.kt = s.kT; bd.dot = s.doT; bd.delta = s.delta; bd.dkv_part = nullptr;
-    bd.dq = s.d_qkv; bd.dk = at(s.d_qkv, d, dt); bd.dv = at(s.d_qkv, 2 * d, dt);
-    bd.lddq = bd.lddk = bd.lddv = 3 * d;
-    RC(attention_bwd(st, dt, bd));
-    // ---- LoRA gradients of q_proj / k_proj (/ v_proj) (rank-r products on the VALU, lora.hip) ----
-    const bool qk_pair = R.q.a && R.k.a;
-    if (R.q.a || R.k.a || R.v.a) RC(layernorm_fwd(st, dt, S.x_in, L.ln1_w, L.ln1_b, s.n, M, d, c.ln_eps));      // n1 recomputed (not stashed)
-    if (qk_pair) {
-      // u = [dq . B_q * (scaling * qscale) | dk . B_k * scaling]  [M, 128] (columns 0..r-1 and 64..64+r-1)
-      RC(lora_down2(st, dt, s.d_qkv, at(s.d_qkv, d, dt), 3 * d, S.bqT, S.bkT, s.u, at(s.u, 64, dt), 128, M, d, r, lora->scaling * qscale, lora->scaling));
-      // d lora_A [r, d] = u^T . n;  d lora_B [d, r] = scale * dq^T . t
-      const LoraWgradItem items[4] = {{s.n, d, s.u, 128, G.q.a, d, 0, 1.0f}, {s.n, d, at(s.u, 64, dt), 128, G.k.a, d, 0, 1.0f},
-                                      {s.d_qkv, 3 * d, S.t, 128, G.q.b, d, 1, lora->scaling * qscale},
-                                      {at(s.d_qkv, d, dt), 3 * d, at(S.t, 64, dt), 128, G.k.b, d, 1, lora->scaling}};
-      RC(lora_wgrad_batch(st, dt, items, 4, M, r, s.wg, wg_floats));      // (one reduce launch for the four)
-    } else {
-      if (R.q.a) RC(lora_apply_bwd(st, dt, s.n, d, s.d_qkv, 3 * d, S.bqT, S.t, s.u, G.q, M, d, d, r, lora->scaling * qscale, s.wg, wg_floats));
-      if (R.k.a) RC(lora_apply_bwd(st, dt, s.n, d, at(s.d_qkv, d, dt), 3 * d, S.bkT, at(S.t, 64, dt), at(s.u, 64, dt), G.k, M, d, d, r, lora->scaling, s.wg, wg_floats));
-    }
-    if (R.v.a) RC(lora_apply_bwd(st, dt, s.n, d, at(s.d_qkv, 2 * d, dt), 3 * d, S.bvT, S.t2, s.u2, G.v, M, d, d, r, lora->scaling, s.wg, wg_floats));
-    if (l == 0) break;   // nothing trainable below layer 0
-    // ---- d n1 = d qkv . Wqkv + u . [A_q ; A_k (; A_v)], then LN1 backward into the residual stream ----
-    if (l == 0) break;      // nothing below the first layer is trainable (frozen conv stem and positions): its input gradient has no consumer
-    RC(gemm(st, dt, lin(s.d_qkv, L.wqkv_t, s.d_n, M, d, 3 * d)));
-    if (qk_pair) {
-      RC(lora_up2(st, dt, s.u, at(s.u, 64, dt), 128, R.q.a, R.k.a, s.d_n, s.d_n, d, M, d, d, r, 1.0f, 1.0f));      // (same rows: one pass, q term then k term)
-    } else {
-      if (R.q.a) RC(lora_up(st, dt, s.u, 128, R.q.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-      if (R.k.a) RC(lora_up(st, dt, at(s.u, 64, dt), 128, R.k.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    }
-    if (R.v.a) RC(lora_up(st, dt, s.u2, 128, R.v.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    RC(layernorm_bwd(st, dt, s.d_n, S.x_in, L.ln1_w, s.dx, s.dx, M, d, c.ln_eps));
-  }
-  return UVX_OK;
+  D.kv_len = audio_lens ? s.t.kvlen : nullptr;          // written by the forward pass (same audio_lens)
+  // ln_post backward: out = LN(x_final); x_final is the running state after the last layer (s.t.x)
+  RC(layernorm_bwd(st, c.dtype, d_out, s.t.x, w->lnf_w, nullptr, s.t.dx, D.M(), c.enc_d, c.ln_eps));
+  return enc_stack_bwd_pre_ln(st, D, s.t, w->layers, lora, grads);
 }
 
 // =====================================================================================

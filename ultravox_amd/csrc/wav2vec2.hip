@@ -13,40 +13,13 @@
 //   -> LayerNorm -> layers x { x = LN(x + attn(x));  x = LN(x + fc2(gelu(fc1(x)))) }   -> last_hidden_state [B, T, d]
 //
 // Rounding points are torch's module-by-module bf16 rounding (conv / norm / activation / linear / residual outputs).
-#include "common.h"
-#include "kernels.h"
+#include "host_util.h"
+#include "enc_stack.h"
 #include "../../include/uvx.h"
 
 namespace {
 
 using namespace uvx;
-
-struct Arena {
-  char* base;
-  size_t cap;
-  size_t off = 0;
-  Arena(void* b, size_t c) : base((char*)b), cap(c) {}
-  void* take(size_t bytes) {
-    const size_t a = (off + 255) & ~(size_t)255;
-    off = a + bytes;
-    return base ? (void*)(base + a) : nullptr;
-  }
-  bool fits() const { return !base || off <= cap; }
-};
-inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-inline char* at(const void* p, size_t elems, int dtype) { return (char*)p + elems * esz(dtype); }
-#define RC(expr)            \
-  do {                      \
-    int _rc = (expr);       \
-    if (_rc) return _rc;    \
-  } while (0)
-
-GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) {
-  GemmDesc g;
-  g.A = A; g.B = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
-  return g;
-}
 
 constexpr int K0P = 64;     // the first conv's kernel (10 taps) zero padded to one GEMM K-tile
 constexpr int GN_ROWS = 512;  // time rows per GroupNorm partial block
@@ -166,30 +139,13 @@ __global__ void w2v_pos_finish_k(T* __restrict__ h, const float* __restrict__ ac
 
 inline unsigned g1(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
-// per-layer stash of the LoRA-training forward (uvx_wav2vec2_fwd_train -> uvx_wav2vec2_bwd).  x_in = the layer's input (pre-LN: the residual
-// stream h; post-LN: the normalised x), mid = x_in + attention branch, y2 = LN1(mid) + feed-forward branch (post-LN only: the input of
-// final_layer_norm), pre = fc1's pre-activation; t / t2 = the adapters' down-projections [M, 128] (q | k and v | out_proj), b?T = lora_B^T [r, d]
-struct W2vLayerStash {
-  void *x_in, *qkv, *o, *mid, *y2, *pre, *t, *t2, *bqT, *bkT, *bvT, *boT;
-  float* lse;
-};
 struct W2vWs {
   int T[9];          // frames after conv layer i
-  int Tn, Tp, M, nchunk;
-  void *im2col, *bufA, *bufB, *x, *n, *qkv, *vt, *o, *o2, *f, *xg;
+  int Tn, nchunk;
+  void *im2col, *bufA, *bufB, *xg;
   float *part, *stat, *acc;
-  // training only
-  char* slots; size_t slot_bytes; W2vLayerStash ls0;
-  void *dx, *d_n, *d_o, *d_f, *d_qkv, *qT, *kT, *doT, *u, *u2;
-  float *delta, *wg;
+  EncStackWs t;      // the shared layer stack's buffers (enc_stack.h); t.x = the hidden states the stem leaves
 };
-W2vLayerStash w2v_layer(const W2vWs& w, int l) {
-  W2vLayerStash s = w.ls0;
-  const size_t off = w.slot_bytes * l;
-  void** ps[] = {&s.x_in, &s.qkv, &s.o, &s.mid, &s.y2, &s.pre, &s.t, &s.t2, &s.bqT, &s.bkT, &s.bvT, &s.boT, (void**)&s.lse};
-  for (void** q : ps) if (*q) *q = (char*)*q + off;
-  return s;
-}
 
 int frames(const uvx_w2v_config_t& c, int L, int* T) {
   int n = L;
@@ -201,51 +157,29 @@ int frames(const uvx_w2v_config_t& c, int L, int* T) {
   return n;
 }
 
+// what this tower asks of the shared stack: either layer form, no mask, the attention adapters only, one launch per adapter product and GELU pass
+EncStackDesc stack_desc(const uvx_w2v_config_t& c, int B, int Tn, bool train) {
+  EncStackDesc D = {};
+  D.dtype = c.dtype; D.d = c.d; D.heads = c.heads; D.ffn = c.ffn; D.layers = c.layers; D.ln_eps = c.ln_eps;
+  D.B = B; D.T = Tn; D.Tp = rup(Tn, 64);
+  D.train = train; D.post_ln = !c.stable_ln; D.key_padding = false;
+  return D;
+}
 W2vWs carve(Arena& a, const uvx_w2v_config_t& c, int B, int L, bool train = false) {
   W2vWs w = {};
   w.Tn = frames(c, L, w.T);
   if (w.Tn <= 0) return w;
   const size_t es = esz(c.dtype);
-  const int C = c.conv_dim, d = c.d, dh = d / c.heads;
-  w.Tp = rup(w.Tn, 64);
-  w.M = B * w.Tn;
+  const int C = c.conv_dim, d = c.d;
   w.nchunk = (w.T[0] + GN_ROWS - 1) / GN_ROWS;
   w.im2col = a.take((size_t)B * w.T[0] * K0P * es);
   w.bufA = a.take((size_t)B * w.T[0] * C * es);
   w.bufB = a.take((size_t)B * (c.n_conv > 1 ? w.T[1] : 1) * C * es);
   w.part = (float*)a.take(sizeof(float) * (size_t)B * w.nchunk * C * 2);
   w.stat = (float*)a.take(sizeof(float) * (size_t)B * C * 2);
-  w.x = a.take((size_t)w.M * d * es);
-  w.n = a.take((size_t)w.M * d * es);
-  w.qkv = a.take((size_t)w.M * 3 * d * es);
-  w.vt = a.take((size_t)B * c.heads * dh * w.Tp * es);
-  w.o = a.take((size_t)w.M * d * es);
-  w.o2 = c.stable_ln ? a.take((size_t)w.M * d * es) : nullptr;      // second residual-stream buffer of the pre-LN layers
-  w.f = a.take((size_t)w.M * c.ffn * es);
   w.xg = a.take((size_t)B * c.pos_groups * (w.Tn + c.pos_k) * (d / c.pos_groups) * es);
-  w.acc = (float*)a.take(sizeof(float) * (size_t)w.M * d);
-  if (train) {
-    const size_t M = (size_t)w.M;
-    const size_t start = (a.off + 255) & ~(size_t)255;
-    a.off = start;
-    W2vLayerStash& s = w.ls0;
-    s.x_in = a.take(M * d * es); s.qkv = a.take(M * 3 * d * es); s.o = a.take(M * d * es); s.mid = a.take(M * d * es);
-    s.y2 = c.stable_ln ? nullptr : a.take(M * d * es);
-    s.pre = a.take(M * c.ffn * es); s.t = a.take(M * 128 * es); s.t2 = a.take(M * 128 * es);
-    s.bqT = a.take((size_t)64 * d * es); s.bkT = a.take((size_t)64 * d * es); s.bvT = a.take((size_t)64 * d * es); s.boT = a.take((size_t)64 * d * es);
-    s.lse = (float*)a.take(sizeof(float) * (size_t)B * c.heads * w.Tn);
-    a.off = (a.off + 255) & ~(size_t)255;
-    w.slot_bytes = a.off - start;
-    w.slots = a.base ? a.base + start : nullptr;
-    a.off = start + w.slot_bytes * c.layers;
-    w.dx = a.take(M * d * es); w.d_n = a.take(M * d * es); w.d_o = a.take(M * d * es);
-    w.d_f = a.take(M * c.ffn * es); w.d_qkv = a.take(M * 3 * d * es);
-    const size_t ht = (size_t)B * c.heads * dh * w.Tp * es;
-    w.qT = a.take(ht); w.kT = a.take(ht); w.doT = a.take(ht);
-    w.u = a.take(M * 128 * es); w.u2 = a.take(M * 128 * es);
-    w.delta = (float*)a.take(sizeof(float) * (size_t)B * c.heads * w.Tn);
-    w.wg = (float*)a.take(sizeof(float) * (size_t)lora_wgrad_scratch_floats(w.M, d, 64));
-  }
+  w.acc = (float*)a.take(sizeof(float) * (size_t)B * w.Tn * d);
+  w.t = enc_stack_carve(a, stack_desc(c, B, w.Tn, train));
   return w;
 }
 
@@ -260,6 +194,14 @@ int check(const uvx_w2v_config_t* c) {
                 (c->pos_k * (c->d / c->pos_groups)) % 64 == 0,
             UVX_ERR_SHAPE, "wav2vec2: hidden %d / heads %d / positional-conv groups %d, kernel %d unsupported", c->d, c->heads,
             c->pos_groups, c->pos_k);
+  return UVX_OK;
+}
+
+// only the attention projections' adapters are built for this tower (EncStackDesc::mlp_adapters = false): forward and backward both refuse the rest
+int refuse_mlp_adapters(const uvx_encoder_lora_t* lora, int layers) {
+  for (int l = 0; l < layers; ++l)
+    UVX_CHECK(!lora->layers[l].g.a && !lora->layers[l].u.a && !lora->layers[l].d.a, UVX_ERR_UNSUPPORTED,
+              "wav2vec2 LoRA: layer %d has a feed-forward adapter (the attention projections q / k / v / out_proj are built for this tower)", l);
   return UVX_OK;
 }
 
@@ -288,9 +230,7 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
   hipStream_t st = (hipStream_t)stream;
   const bool train = lora != nullptr;
   if (train) RC(lora_check(lora, c.layers, nullptr, "wav2vec2 LoRA"));
-  for (int l = 0; train && l < c.layers; ++l)
-    UVX_CHECK(!lora->layers[l].g.a && !lora->layers[l].u.a && !lora->layers[l].d.a, UVX_ERR_UNSUPPORTED,
-              "wav2vec2 LoRA: layer %d has a feed-forward adapter (the attention projections q / k / v / out_proj are built for this tower)", l);
+  if (train) RC(refuse_mlp_adapters(lora, c.layers));
   for (int i = 0; i < c.n_conv; ++i) {
     UVX_CHECK(!c.conv_bias || w->conv_b[i], UVX_ERR_INVALID, "wav2vec2_fwd: conv_bias is set but conv layer %d has no bias", i);
     UVX_CHECK(!c.feat_norm_layer || (w->conv_ln_w[i] && w->conv_ln_b[i]), UVX_ERR_INVALID, "wav2vec2_fwd: conv layer %d has no layer norm", i);
@@ -301,7 +241,8 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
   W2vWs s = carve(a, c, B, L, train);
   UVX_CHECK(s.Tn > 0, UVX_ERR_SHAPE, "wav2vec2_fwd: %d samples are shorter than the conv stack's receptive field", L);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "wav2vec2_fwd: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, C = c.conv_dim, d = c.d, dh = d / c.heads, M = s.M, Tn = s.Tn;
+  const int dt = c.dtype, C = c.conv_dim, d = c.d, M = B * s.Tn, Tn = s.Tn;
+  const EncStackDesc D = stack_desc(c, B, Tn, train);
   UVX_CHECK(dt == DT_BF16 || values_is_f32, UVX_ERR_INVALID, "wav2vec2_fwd: f32 mode needs f32 input_values");
 
   // ---- feature encoder ----
@@ -354,7 +295,7 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
   // ---- feature projection: LayerNorm(C) -> Linear(C, d) ----
   RC(layernorm_fwd(st, dt, cur, w->fp_ln_w, w->fp_ln_b, nxt, M, C, c.ln_eps));
   {
-    GemmDesc g = lin(nxt, w->fp_w, s.x, M, d, C);
+    GemmDesc g = lin(nxt, w->fp_w, s.t.x, M, d, C);
     g.bias = w->fp_b;
     RC(gemm(st, dt, g));
   }
@@ -362,8 +303,8 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
   {
     const int G = c.pos_groups, dg = d / G, K = c.pos_k, R = Tn + K;
     const long long n8 = (long long)B * G * R * dg / 8;
-    if (dt == DT_BF16) hipLaunchKernelGGL(w2v_pos_pack_k<bf16_t>, dim3(g1(n8, 256)), dim3(256), 0, st, (const bf16_t*)s.x, (bf16_t*)s.xg, n8, Tn, d, G, K);
-    else hipLaunchKernelGGL(w2v_pos_pack_k<float>, dim3(g1(n8, 256)), dim3(256), 0, st, (const float*)s.x, (float*)s.xg, n8, Tn, d, G, K);
+    if (dt == DT_BF16) hipLaunchKernelGGL(w2v_pos_pack_k<bf16_t>, dim3(g1(n8, 256)), dim3(256), 0, st, (const bf16_t*)s.t.x, (bf16_t*)s.xg, n8, Tn, d, G, K);
+    else hipLaunchKernelGGL(w2v_pos_pack_k<float>, dim3(g1(n8, 256)), dim3(256), 0, st, (const float*)s.t.x, (float*)s.xg, n8, Tn, d, G, K);
     UVX_LAUNCH_CHECK();
     for (int b = 0; b < B; ++b) {   // one batched GEMM per clip: batch = groups (their weights differ, the clip's do not)
       GemmDesc g = lin(at(s.xg, (size_t)b * G * R * dg, dt), w->pos_w, s.acc + (size_t)b * Tn * d, Tn, dg, K * dg);
@@ -372,101 +313,26 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
       RC(gemm(st, dt, g));
     }
     const long long m8 = (long long)M * d / 8;
-    if (dt == DT_BF16) hipLaunchKernelGGL(w2v_pos_finish_k<bf16_t>, dim3(g1(m8, 256)), dim3(256), 0, st, (bf16_t*)s.x, s.acc, (const bf16_t*)w->pos_b, m8, d);
-    else hipLaunchKernelGGL(w2v_pos_finish_k<float>, dim3(g1(m8, 256)), dim3(256), 0, st, (float*)s.x, s.acc, (const float*)w->pos_b, m8, d);
+    if (dt == DT_BF16) hipLaunchKernelGGL(w2v_pos_finish_k<bf16_t>, dim3(g1(m8, 256)), dim3(256), 0, st, (bf16_t*)s.t.x, s.acc, (const bf16_t*)w->pos_b, m8, d);
+    else hipLaunchKernelGGL(w2v_pos_finish_k<float>, dim3(g1(m8, 256)), dim3(256), 0, st, (float*)s.t.x, s.acc, (const float*)w->pos_b, m8, d);
     UVX_LAUNCH_CHECK();
   }
-  const float qscale = 1.0f / sqrtf((float)dh);
-  // one attention branch: q|k|v projection of `in` (+ adapters), attention, out_proj + residual `res` (+ adapter) -> `dst`
-  auto attn_branch = [&](int l, const void* in, const void* res, void* dst) -> int {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    W2vLayerStash S = train ? w2v_layer(s, l) : W2vLayerStash{};
-    void* qkv = train ? S.qkv : s.qkv;
-    void* o = train ? S.o : s.o;
-    {
-      GemmDesc g = lin(in, Lw.wqkv, qkv, M, 3 * d, d);
-      g.bias = Lw.bqkv;
-      RC(gemm(st, dt, g));
-    }
-    if (train) {      // peft: result += lora_B(lora_A(x)) * scaling; q carries head_dim^-0.5 (folded into the packed q rows)
-      const uvx_enc_lora_layer_t& R = lora->layers[l];
-      if (R.q.a) RC(lora_apply(st, dt, in, d, R.q, S.bqT, S.t, qkv, 3 * d, M, d, d, lora->r, lora->scaling * qscale));
-      if (R.k.a) RC(lora_apply(st, dt, in, d, R.k, S.bkT, at(S.t, 64, dt), at(qkv, d, dt), 3 * d, M, d, d, lora->r, lora->scaling));
-      if (R.v.a) RC(lora_apply(st, dt, in, d, R.v, S.bvT, S.t2, at(qkv, 2 * d, dt), 3 * d, M, d, d, lora->r, lora->scaling));
-    }
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(qkv, 2 * d, dt), s.vt, B, Tn, s.Tp, c.heads, dh, 3 * d));
-    AttnDesc ad;
-    ad.q = qkv; ad.k = at(qkv, d, dt); ad.v = at(qkv, 2 * d, dt); ad.vt = s.vt; ad.o = o; ad.lse = train ? S.lse : nullptr;
-    ad.B = B; ad.T = Tn; ad.Tp = s.Tp; ad.Hq = c.heads; ad.Hkv = c.heads; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = 3 * d; ad.ldo = d; ad.causal = 0; ad.block = 0;
-    ad.scale = 1.0f;   // q_proj (weight and bias) pre-scaled by head_dim^-0.5 at pack time: exact for a power of two
-    RC(attention_fwd(st, dt, ad));
-    {
-      GemmDesc g = lin(o, Lw.wo, dst, M, d, d);
-      g.bias = Lw.bo; g.residual = res; g.ldr = d;
-      RC(gemm(st, dt, g));
-    }
-    if (train && lora->layers[l].o.a) RC(lora_apply(st, dt, o, d, lora->layers[l].o, S.boT, at(S.t2, 64, dt), dst, d, M, d, d, lora->r, lora->scaling));
-    return UVX_OK;
-  };
-  // one feed-forward branch: fc1 + GELU (training: the pre-activation is kept), fc2 + residual `res` -> `dst`
-  auto ffn_branch = [&](int l, const void* in, const void* res, void* dst) -> int {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    if (train) {
-      W2vLayerStash S = w2v_layer(s, l);
-      GemmDesc g = lin(in, Lw.fc1_w, S.pre, M, c.ffn, d);
-      g.bias = Lw.fc1_b;
-      RC(gemm(st, dt, g));
-      RC(gelu_fwd(st, dt, S.pre, s.f, (long long)M * c.ffn));
-    } else {
-      GemmDesc g = lin(in, Lw.fc1_w, s.f, M, c.ffn, d);
-      g.bias = Lw.fc1_b; g.act = 1;
-      RC(gemm(st, dt, g));
-    }
-    GemmDesc g = lin(s.f, Lw.fc2_w, dst, M, d, c.ffn);
-    g.bias = Lw.fc2_b; g.residual = res; g.ldr = d;
-    return gemm(st, dt, g);
-  };
   if (c.stable_ln) {
-    // ---- encoder, do_stable_layer_norm = True ([3P] Wav2Vec2EncoderStableLayerNorm / ...EncoderLayerStableLayerNorm): per layer
-    //      h = h + attention(layer_norm(h));  h = h + feed_forward(final_layer_norm(h));  encoder.layer_norm after the last layer ----
-    // inference: the residual stream alternates between s.x and s.o2; training: it lives in the layer stashes (x_in -> mid -> next x_in)
-    void* h = s.x;
+    // ---- encoder, do_stable_layer_norm = True ([3P] Wav2Vec2EncoderStableLayerNorm / ...EncoderLayerStableLayerNorm): pre-LN layers,
+    //      encoder.layer_norm after the last one.  Training: the residual stream starts in layer 0's stash and ends in s.t.x (kept for the backward) ----
+    void* h = s.t.x;
     if (train && c.layers > 0) {
-      UVX_HIP(hipMemcpyAsync(w2v_layer(s, 0).x_in, s.x, (size_t)M * d * esz(dt), hipMemcpyDeviceToDevice, st));
-      h = w2v_layer(s, 0).x_in;
+      h = enc_stack_layer(s.t, 0).x_in;
+      UVX_HIP(hipMemcpyAsync(h, s.t.x, (size_t)M * d * esz(dt), hipMemcpyDeviceToDevice, st));
     }
-    for (int l = 0; l < c.layers; ++l) {
-      const uvx_enc_layer_t& Lw = w->layers[l];
-      void* h2 = train ? w2v_layer(s, l).mid : s.o2;
-      void* h_next = !train ? h : (l + 1 < c.layers ? w2v_layer(s, l + 1).x_in : s.x);
-      RC(layernorm_fwd(st, dt, h, Lw.ln1_w, Lw.ln1_b, s.n, M, d, c.ln_eps));
-      RC(attn_branch(l, s.n, h, h2));
-      RC(layernorm_fwd(st, dt, h2, Lw.ln2_w, Lw.ln2_b, s.n, M, d, c.ln_eps));
-      RC(ffn_branch(l, s.n, h2, h_next));
-      h = h_next;
-    }
-    return layernorm_fwd(st, dt, h, w->ln_w, w->ln_b, out, M, d, c.ln_eps);      // (training: h == s.x, kept for the backward)
+    RC(enc_stack_fwd_pre_ln(st, D, s.t, w->layers, lora, h));
+    return layernorm_fwd(st, dt, h, w->ln_w, w->ln_b, out, M, d, c.ln_eps);
   }
-  // ---- encoder (post-LN, do_stable_layer_norm = False): x = LN(x + attention(x)); x = LN(x + feed_forward(x)) ----
-  // inference: x alternates between s.n and s.x; training: x_in / mid / y2 of the layer stashes, x1 = LN1(mid) in s.n
-  void* x = train && c.layers > 0 ? w2v_layer(s, 0).x_in : s.n;
-  void* y = s.x;
-  RC(layernorm_fwd(st, dt, s.x, w->ln_w, w->ln_b, x, M, d, c.ln_eps));
-  for (int l = 0; l < c.layers; ++l) {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    void* mid = train ? w2v_layer(s, l).mid : y;
-    void* x1 = train ? s.n : x;
-    void* y2 = train ? w2v_layer(s, l).y2 : y;
-    RC(attn_branch(l, x, x, mid));
-    RC(layernorm_fwd(st, dt, mid, Lw.ln1_w, Lw.ln1_b, x1, M, d, c.ln_eps));       // layers.N.layer_norm
-    RC(ffn_branch(l, x1, x1, y2));
-    void* dst = l + 1 == c.layers ? out : (train ? w2v_layer(s, l + 1).x_in : x);
-    RC(layernorm_fwd(st, dt, y2, Lw.ln2_w, Lw.ln2_b, dst, M, d, c.ln_eps));     // layers.N.final_layer_norm
-    x = dst;
-  }
+  // ---- encoder (post-LN, do_stable_layer_norm = False): encoder.layer_norm in front of the layers; the last layer writes `out` ----
+  void* x = train && c.layers > 0 ? enc_stack_layer(s.t, 0).x_in : s.t.n;
+  RC(layernorm_fwd(st, dt, s.t.x, w->ln_w, w->ln_b, x, M, d, c.ln_eps));
   if (c.layers == 0) UVX_HIP(hipMemcpyAsync(out, x, (size_t)M * d * esz(dt), hipMemcpyDeviceToDevice, st));
-  return UVX_OK;
+  return enc_stack_fwd_post_ln(st, D, s.t, w->layers, lora, x, out);
 }
 
 extern "C" int32_t uvx_wav2vec2_fwd(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_weights_t* w, const void* input_values,
@@ -497,94 +363,19 @@ extern "C" int32_t uvx_wav2vec2_bwd(void* stream, const uvx_w2v_config_t* cfg, c
   UVX_CHECK(w && w->layers && lora && d_out && grads && grads->layers && workspace, UVX_ERR_INVALID, "wav2vec2_bwd: null argument");
   const uvx_w2v_config_t& c = *cfg;
   RC(lora_check(lora, c.layers, grads, "wav2vec2_bwd"));
+  RC(refuse_mlp_adapters(lora, c.layers));
   hipStream_t st = (hipStream_t)stream;
   if (B == 0 || c.layers == 0) return UVX_OK;
   Arena a(workspace, ws_bytes);
   W2vWs s = carve(a, c, B, L, true);
   UVX_CHECK(s.Tn > 0, UVX_ERR_SHAPE, "wav2vec2_bwd: %d samples are shorter than the conv stack's receptive field", L);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "wav2vec2_bwd: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, d = c.d, dh = d / c.heads, M = s.M, Tn = s.Tn, r = lora->r;
-  const float qscale = 1.0f / sqrtf((float)dh);
-  const long long wg_floats = lora_wgrad_scratch_floats(s.M, d, 64);
-  // gradient of the attention branch's output `dy` [M, d] (d_o scratch: s.d_o) -> adapter gradients; unless `last`, d (branch input) in s.d_n =
-  // d qkv . Wqkv + u . A (+ `add`: the residual path's gradient, folded into the dgrad's epilogue)
-  auto attn_branch_bwd = [&](int l, const void* dy, const void* add, bool last) -> int {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    UVX_CHECK(Lw.wqkv_t && Lw.wo_t && Lw.fc1_t && Lw.fc2_t, UVX_ERR_INVALID, "wav2vec2_bwd: layer %d lacks transposed weights", l);
-    W2vLayerStash S = w2v_layer(s, l);
-    const uvx_enc_lora_layer_t& R = lora->layers[l];
-    const uvx_enc_lora_layer_grads_t& G = grads->layers[l];
-    // the branch input: pre-LN = layer_norm(x_in), recomputed; post-LN = x_in itself
-    const void* in = S.x_in;
-    if (c.stable_ln) {
-      RC(layernorm_fwd(st, dt, S.x_in, Lw.ln1_w, Lw.ln1_b, s.n, M, d, c.ln_eps));
-      in = s.n;
-    }
-    RC(gemm(st, dt, lin(dy, Lw.wo_t, s.d_o, M, d, d)));
-    if (R.o.a) {
-      RC(lora_apply_bwd(st, dt, S.o, d, dy, d, S.boT, at(S.t2, 64, dt), at(s.u2, 64, dt), G.o, M, d, d, r, lora->scaling, s.wg, wg_floats));
-      RC(lora_up(st, dt, at(s.u2, 64, dt), 128, R.o.a, 1, s.d_o, d, M, d, r, 1.0f, 1));
-    }
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, S.qkv, s.qT, B, Tn, s.Tp, c.heads, dh, 3 * d));
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(S.qkv, d, dt), s.kT, B, Tn, s.Tp, c.heads, dh, 3 * d));
-    if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, s.d_o, s.doT, B, Tn, s.Tp, c.heads, dh, d));
-    AttnBwdDesc bd;
-    AttnDesc& ad = bd.f;
-    ad.q = S.qkv; ad.k = at(S.qkv, d, dt); ad.v = at(S.qkv, 2 * d, dt); ad.o = S.o; ad.lse = S.lse;
-    ad.B = B; ad.T = Tn; ad.Tp = s.Tp; ad.Hq = c.heads; ad.Hkv = c.heads; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = 3 * d; ad.ldo = d; ad.causal = 0; ad.block = 0; ad.scale = 1.0f;
-    bd.dout = s.d_o; bd.qt = s.qT; bd.kt = s.kT; bd.dot = s.doT; bd.delta = s.delta; bd.dkv_part = nullptr;
-    bd.dq = s.d_qkv; bd.dk = at(s.d_qkv, d, dt); bd.dv = at(s.d_qkv, 2 * d, dt);
-    bd.lddq = bd.lddk = bd.lddv = 3 * d;
-    RC(attention_bwd(st, dt, bd));
-    if (R.q.a) RC(lora_apply_bwd(st, dt, in, d, s.d_qkv, 3 * d, S.bqT, S.t, s.u, G.q, M, d, d, r, lora->scaling * qscale, s.wg, wg_floats));
-    if (R.k.a) RC(lora_apply_bwd(st, dt, in, d, at(s.d_qkv, d, dt), 3 * d, S.bkT, at(S.t, 64, dt), at(s.u, 64, dt), G.k, M, d, d, r, lora->scaling, s.wg, wg_floats));
-    if (R.v.a) RC(lora_apply_bwd(st, dt, in, d, at(s.d_qkv, 2 * d, dt), 3 * d, S.bvT, S.t2, s.u2, G.v, M, d, d, r, lora->scaling, s.wg, wg_floats));
-    if (last) return UVX_OK;
-    {
-      GemmDesc g = lin(s.d_qkv, Lw.wqkv_t, s.d_n, M, d, 3 * d);
-      g.residual = add; g.ldr = d;
-      RC(gemm(st, dt, g));
-    }
-    if (R.q.a) RC(lora_up(st, dt, s.u, 128, R.q.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    if (R.k.a) RC(lora_up(st, dt, at(s.u, 64, dt), 128, R.k.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    if (R.v.a) RC(lora_up(st, dt, s.u2, 128, R.v.a, 1, s.d_n, d, M, d, r, 1.0f, 1));
-    return UVX_OK;
-  };
-  // gradient of the feed-forward branch's output `dy` -> s.d_n = (dy . W_fc2 * gelu'(pre)) . W_fc1 (+ `add`)
-  auto ffn_branch_bwd = [&](int l, const void* dy, const void* add) -> int {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    W2vLayerStash S = w2v_layer(s, l);
-    RC(gemm(st, dt, lin(dy, Lw.fc2_t, s.d_f, M, c.ffn, d)));
-    RC(gelu_bwd(st, dt, s.d_f, S.pre, s.d_f, (long long)M * c.ffn));
-    GemmDesc g = lin(s.d_f, Lw.fc1_t, s.d_n, M, d, c.ffn);
-    g.residual = add; g.ldr = d;
-    return gemm(st, dt, g);
-  };
+  EncStackDesc D = stack_desc(c, B, s.Tn, true);
+  D.who = "wav2vec2_bwd";
   if (c.stable_ln) {
-    // out = encoder.layer_norm(h_final); h_final = s.x (left there by the forward)
-    RC(layernorm_bwd(st, dt, d_out, s.x, w->ln_w, nullptr, s.dx, M, d, c.ln_eps));
-    for (int l = c.layers - 1; l >= 0; --l) {
-      const uvx_enc_layer_t& Lw = w->layers[l];
-      W2vLayerStash S = w2v_layer(s, l);
-      RC(ffn_branch_bwd(l, s.dx, nullptr));                                                     // d n2 in s.d_n
-      RC(layernorm_bwd(st, dt, s.d_n, S.mid, Lw.ln2_w, s.dx, s.dx, M, d, c.ln_eps));           // d h2 = d h + LN2'(d n2)
-      RC(attn_branch_bwd(l, s.dx, nullptr, l == 0));                                            // d n1 in s.d_n
-      if (l == 0) break;
-      RC(layernorm_bwd(st, dt, s.d_n, S.x_in, Lw.ln1_w, s.dx, s.dx, M, d, c.ln_eps));          // d h = d h2 + LN1'(d n1)
-    }
-    return UVX_OK;
+    // out = encoder.layer_norm(h_final); h_final = s.t.x (left there by the forward)
+    RC(layernorm_bwd(st, c.dtype, d_out, s.t.x, w->ln_w, nullptr, s.t.dx, D.M(), c.d, c.ln_eps));
+    return enc_stack_bwd_pre_ln(st, D, s.t, w->layers, lora, grads);
   }
-  // post-LN: the layer's output = final_layer_norm(y2), y2 = x1 + ffn(x1), x1 = layer_norm(mid), mid = x_in + attention(x_in)
-  const void* dx = d_out;
-  for (int l = c.layers - 1; l >= 0; --l) {
-    const uvx_enc_layer_t& Lw = w->layers[l];
-    W2vLayerStash S = w2v_layer(s, l);
-    RC(layernorm_bwd(st, dt, dx, S.y2, Lw.ln2_w, nullptr, s.dx, M, d, c.ln_eps));               // d y2 in s.dx
-    RC(ffn_branch_bwd(l, s.dx, s.dx));                                                          // d x1 = d y2 + ffn'(d y2) in s.d_n
-    RC(layernorm_bwd(st, dt, s.d_n, S.mid, Lw.ln1_w, nullptr, s.dx, M, d, c.ln_eps));           // d mid in s.dx
-    RC(attn_branch_bwd(l, s.dx, s.dx, l == 0));                                                 // d x_in = d mid + attention'(d mid) in s.d_n
-    dx = s.d_n;
-  }
-  return UVX_OK;
+  return enc_stack_bwd_post_ln(st, D, s.t, w->layers, lora, grads, d_out);
 }
