@@ -43,6 +43,8 @@ What is recorded
                     module set, trainable names, state-dict key names, forward outputs and adapter gradients.
   lora_targets_reference.npz / .json — the same with target_modules beyond the default: q / k / v / out_proj (Whisper) and q / k / v /
                     o_proj (Llama, GQA), and a v + o-only list; peft's error text for a list that hits nothing.
+  llm_ws_bytes.json — NOT from the reference: uvx_llm_ws_bytes of THIS repository's library over a grid of configurations (see
+                    llm_ws_bytes_cases: regenerate only from a commit whose workspace sizes are meant to change).
   lora_w2v_reference.npz / .json — the REFERENCE apply_lora on an installed-HF Wav2Vec2Model (the AutoModel tower, both encoder families): adapted
                     modules and names, last_hidden_state, adapter gradients.
 """
@@ -1161,6 +1163,44 @@ def projector_live_cases():
     np.savez_compressed(os.path.join(HERE, "projector_live_reference.npz"), x=x.numpy(), y=y.numpy(),
                         **{"w." + k: v.numpy() for k, v in proj.state_dict().items()})
     print("projector_live_reference.npz", list(proj.state_dict()))
+
+
+# REGENERATE ONLY FROM A COMMIT WHOSE WORKSPACE SIZES ARE MEANT TO CHANGE.  The fixture pins what uvx_llm_ws_bytes returned when it was written, so
+# that a change to how the LLM workspace is described or carved cannot move a byte unnoticed (tests/test_llm_ws_bytes_cpu.py); regenerating it from
+# the commit under test makes that test vacuous.  Host arithmetic only: the library loads without a GPU.
+LLM_WS_SHAPES = {   # hidden, heads, kv heads, head_dim, intermediate, layers, vocab
+    "tiny": dict(llm_d=192, llm_heads=4, llm_kv_heads=2, llm_head_dim=64, llm_inter=512, llm_layers=3, vocab=512),
+    "llama3_8b": dict(llm_d=4096, llm_heads=32, llm_kv_heads=8, llm_head_dim=128, llm_inter=14336, llm_layers=32, vocab=128256),
+}
+LLM_WS_FLAVOURS = {   # llm_flavor, llm_act, llm_qk_norm
+    "llama": (0, 0, 0), "qwen3": (0, 0, 1), "gemma": (1, 1, 0), "gemma3": (2, 1, 1),
+}
+
+
+def llm_ws_bytes_grid():
+    """(key, Config fields, B, T, save) of every recorded call; the Llama-3-8B shape in the Llama flavour only."""
+    for shape, dims in LLM_WS_SHAPES.items():
+        for flavour, (fl, act, qkn) in LLM_WS_FLAVOURS.items():
+            if shape != "tiny" and flavour != "llama":
+                continue
+            for wts in (0, 1):
+                for dtype in (0, 1):            # UVX_BF16, UVX_F32
+                    for save in (0, 1):
+                        for (B, T) in ((1, 1), (3, 80), (8, 320)):      # T = 80: Tp != T; B = 3: uneven chain slices
+                            fields = dict(dims, dtype=dtype, llm_flavor=fl, llm_act=act, llm_qk_norm=qkn, llm_wt_stream=wts)
+                            yield f"{shape}/{flavour}/wts{wts}/dt{dtype}/save{save}/B{B}/T{T}", fields, B, T, save
+
+
+def llm_ws_bytes_cases():
+    import ctypes
+    from ultravox_amd import _lib
+    lib = _lib.lib()
+    out = {}
+    for key, fields, B, T, save in llm_ws_bytes_grid():
+        out[key] = int(lib.uvx_llm_ws_bytes(ctypes.byref(_lib.Config(**fields)), B, T, save))
+    with open(os.path.join(HERE, "llm_ws_bytes.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("llm_ws_bytes.json", len(out))
 
 
 if __name__ == "__main__":

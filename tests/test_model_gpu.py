@@ -412,6 +412,54 @@ def test_two_stream_llm_schedule_is_bit_identical(B, T):
     assert torch.isfinite(one[2].float()).all() and one[2].float().abs().max() > 0
 
 
+@pytest.mark.parametrize("family", ["qwen3", "gemma3"])
+def test_llm_chains_are_bit_identical_with_extra_stash_fields(family):
+    """The same for the flavours whose layer stash holds more than Llama's: Qwen3-style q_norm / k_norm (qk_raw) and Gemma-3 (qk_raw, o_pre, m_pre) -
+    a batch slice must move those buffers too.  bf16, B = 3 (slices of 2 + 1 and 1 + 1 + 1), T = 80 (not a multiple of 64), 2 layers:
+    uvx_llm_fwd(save_for_bwd = 1) + uvx_llm_bwd with 2 and 3 chains give loss, logits and d loss / d inputs_embeds EXACTLY equal to one chain's."""
+    from ultravox_amd import _lib
+    from ultravox_amd.model import UltravoxModel
+    from ultravox_amd.weights import random_state_dict
+    if family == "qwen3":
+        from test_qwen_gpu import _cfg
+        cfg = _cfg("qwen3")
+    else:
+        from test_gemma3_gpu import _cfg
+        cfg = _cfg(layers=2)
+    sd = {k: v.bfloat16() for k, v in random_state_dict(cfg, seed=17).items()}
+    model = UltravoxModel(cfg, state_dict=sd, device=DEV, dtype=torch.bfloat16)
+    assert model._c.llm_qk_norm == 1 and model._c.llm_layers == 2 and model._c.llm_flavor == (2 if family == "gemma3" else 0)
+    B, T = 3, 80
+    torch.manual_seed(6)
+    emb = (torch.randn(B, T, cfg.text_config.hidden_size) * 0.5).bfloat16().to(DEV)
+    labels = torch.randint(0, 512, (B, T)); labels[:, : T // 2] = -100
+    mask = torch.ones(B, T, dtype=torch.long); mask[0, :3] = 0; mask[B - 1, T - 4:] = 0
+    labels[B - 1, T - 4:] = -100
+    labels, mask = labels.to(DEV), mask.to(DEV)
+
+    def run():
+        out = model.language_model_forward(emb, labels=labels, attention_mask=mask, want_logits=True, save_for_bwd=True)
+        assert not model._llm_train_pair
+        d = model.language_model_backward(1.0).clone()
+        torch.cuda.synchronize()
+        return out.loss.clone(), out.logits.clone(), d
+
+    L = _lib.lib()
+    try:
+        L.uvx_set_option(11, 1)
+        one = run()
+        more = []
+        for n in (2, 3):
+            L.uvx_set_option(11, n)
+            more.append(run())
+    finally:
+        L.uvx_set_option(11, 1)                    # the default
+    for other in more:
+        for a, b in zip(one, other):
+            assert torch.equal(a, b)
+    assert torch.isfinite(one[2].float()).all() and one[2].float().abs().max() > 0
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_streamed_weight_transposes_are_bit_identical(dtype):
     """uvx_config_t.llm_wt_stream (UltravoxModel(stream_weight_transposes=True)): the backward's transposed weight copies are

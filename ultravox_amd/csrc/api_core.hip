@@ -1,5 +1,5 @@
 // C-ABI: error reporting + single-op entry points (used by unit tests and by host code that wants
-// one kernel at a time).  The coarse-grained model entry points live in model.hip.
+// one kernel at a time).  The coarse-grained model entry points live in model.hip, llm_stack.hip, generate.hip and wav2vec2.hip.
 #include <stdarg.h>
 #include <string.h>
 #include "common.h"

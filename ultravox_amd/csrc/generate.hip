@@ -11,6 +11,7 @@
 // KV cache layout: [layer][k | v][B][Tmax][kv_heads * head_dim], caller-owned.
 #include <algorithm>
 #include "host_util.h"
+#include "llm_rules.h"
 #include "../../include/uvx.h"
 
 namespace {
@@ -417,13 +418,6 @@ __global__ void greedy_select_k(const T* __restrict__ logits, int V, const int64
   if (still) atomicAdd(&counter[step & 1], 1);
 }
 
-// [3P] transformers 4.51.3 GemmaModel.forward: hidden_states * tensor(hidden_size ** 0.5, dtype) - the normaliser is rounded
-// to the model dtype first (same helper as model.hip)
-float gemma_normalizer(const uvx_config_t& c) {
-  const float n = sqrtf((float)c.llm_d);
-  return c.dtype == DT_BF16 ? bf2f(f2bf(n)) : n;
-}
-
 // one decoder layer on M = B*T rows; attention supplied by the caller
 struct LayerIO { void *x_in, *x_mid; };
 
@@ -483,19 +477,6 @@ int attn_out(hipStream_t st, const uvx_config_t& c, const uvx_llm_layer_t& L, In
   }
   return gemm(st, dt, sk(g, s));
 }
-float attn_scale_of(const uvx_config_t& c) { return c.llm_attn_scale > 0.f ? c.llm_attn_scale : 1.0f / sqrtf((float)c.llm_head_dim); }
-// Gemma-3: post norms present and a local rotary table where layers are flagged
-int g3_check(const uvx_config_t& c, const uvx_llm_weights_t* w, int Tmax) {
-  if (c.llm_flavor != UVX_LLM_GEMMA3) return UVX_OK;
-  bool any_local = false;
-  for (int l = 0; l < c.llm_layers; ++l) {
-    UVX_CHECK(w->layers[l].ln1_post && w->layers[l].ln2_post, UVX_ERR_INVALID, "llm: Gemma-3 layer %d has no post norms", l);
-    any_local = any_local || (w->layer_local && w->layer_local[l]);
-  }
-  UVX_CHECK(!any_local || w->rope_cos_sin_local, UVX_ERR_INVALID, "llm: Gemma-3 sliding-window layers need rope_cos_sin_local");
-  (void)Tmax;
-  return UVX_OK;
-}
 
 // q | k | v projection of a layer (+ Qwen2's biases), then the rotary embedding - for Qwen3 / Gemma-3 behind the per-head q_norm / k_norm
 // (l: the layer index - Gemma-3's sliding-window layers rotate with their own table)
@@ -503,7 +484,7 @@ int qkv_rope(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, 
              const int32_t* pos, int rows, int T, int QKV, int l, const InferWs* ws = nullptr) {
   const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads;
   const bool g3 = c.llm_flavor == UVX_LLM_GEMMA3;
-  const float* rope = g3 && w->layer_local && w->layer_local[l] ? w->rope_cos_sin_local : w->rope_cos_sin;
+  const float* rope = rope_of(c, w, l);
   GemmDesc g = lin(n, L.wqkv, qkv, rows, QKV, c.llm_d);
   g.bias = L.bqkv;
   RC(gemm(st, dt, ws ? sk(g, *ws) : g));
@@ -524,9 +505,7 @@ int qkv_rope_append(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights
     GemmDesc g = lin(n, L.wqkv, s.qkv, rows, s.QKV, c.llm_d);
     g.bias = L.bqkv;
     RC(gemm(st, dt, sk(g, s)));
-    const bool g3 = c.llm_flavor == UVX_LLM_GEMMA3;
-    launch_rope_kv_append<bf16_t>(st, s.qkv, g3 && w->layer_local && w->layer_local[l] ? w->rope_cos_sin_local : w->rope_cos_sin, pos, ck, cv,
-                                  B, Tn, Tmax, t0, Hq, Hkv, dh, s.QKV);
+    launch_rope_kv_append<bf16_t>(st, s.qkv, rope_of(c, w, l), pos, ck, cv, B, Tn, Tmax, t0, Hq, Hkv, dh, s.QKV);
     UVX_LAUNCH_CHECK();
     return UVX_OK;
   }
@@ -562,7 +541,7 @@ extern "C" int32_t uvx_llm_prefill(void* stream, const uvx_config_t* cfg, const 
   const uvx_config_t& c = *cfg;
   UVX_CHECK(T >= 1 && T <= Tmax, UVX_ERR_SHAPE, "llm_prefill: prompt length %d exceeds the cache length %d", T, Tmax);
   UVX_CHECK(w->rope_len >= Tmax, UVX_ERR_SHAPE, "llm_prefill: rope table (%d) shorter than the cache (%d)", w->rope_len, Tmax);
-  RC(g3_check(c, w, T));          // (Gemma-3: post norms + local rotary table present; prompts beyond the window run the WINDOWED kernels)
+  RC(gemma3_check(c, w));         // (post norms + local rotary table present; prompts beyond the window run the WINDOWED kernels)
   hipStream_t st = (hipStream_t)stream;
   Arena a(workspace, ws_bytes);
   InferWs s = carve(a, c, B, T);
@@ -571,8 +550,7 @@ extern "C" int32_t uvx_llm_prefill(void* stream, const uvx_config_t* cfg, const 
   const size_t es = esz(dt);
   hipLaunchKernelGGL(mask_positions_k, dim3(B), dim3(64), 0, st, attention_mask, s.pos, kv_start, s.kvl, next_pos, T);
   UVX_LAUNCH_CHECK();
-  UVX_HIP(hipMemcpyAsync(s.x, inputs_embeds, (size_t)M * D * es, hipMemcpyDeviceToDevice, st));
-  if (c.llm_flavor == UVX_LLM_GEMMA) RC(scale_inplace(st, dt, s.x, (long long)M * D, gemma_normalizer(c)));   // 4.51.3: inside the model
+  RC(embed_in(st, c, s.x, inputs_embeds, M));
   const size_t layer_stride = (size_t)2 * B * Tmax * KVD;  // elements
   bool n1_ready = false, n2_ready = false;      // s.n already holds this layer's input_layernorm / post_attention_layernorm (fused reduces)
   for (int l = 0; l < c.llm_layers; ++l) {
@@ -584,12 +562,9 @@ extern "C" int32_t uvx_llm_prefill(void* stream, const uvx_config_t* cfg, const 
       RC(qkv_rope_append(st, c, w, L, s, s.n, s.pos, B, T, Tmax, 0, ck, cv, l));
     }
     if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(s.qkv, (size_t)(Hq + Hkv) * dh, dt), s.vt, B, T, s.Tp, Hkv, dh, s.QKV));
-    AttnDesc ad;
-    ad.q = s.qkv; ad.k = at(s.qkv, (size_t)Hq * dh, dt); ad.v = at(s.qkv, (size_t)(Hq + Hkv) * dh, dt);
-    ad.vt = s.vt; ad.o = s.o; ad.lse = nullptr; ad.kv_start = kv_start; ad.kv_len = s.kvl;
-    ad.B = B; ad.T = T; ad.Tp = s.Tp; ad.Hq = Hq; ad.Hkv = Hkv; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = s.QKV; ad.ldo = s.OD; ad.causal = 1; ad.scale = attn_scale_of(c);
-    ad.window = c.llm_window > 0 && T > c.llm_window && w->layer_local && w->layer_local[l] ? c.llm_window : 0;
+    AttnDesc ad = causal_gqa_desc(c, s.qkv, B, T, s.Tp, s.QKV, s.OD);
+    ad.vt = s.vt; ad.o = s.o; ad.kv_start = kv_start; ad.kv_len = s.kvl;
+    ad.window = window_of(c, w, l, T);
     RC(attention_fwd(st, dt, ad));
     RC(attn_out(st, c, L, s, M, s.o, s.OD, s.x, s.x2, &n2_ready));
     RC(mlp_block(st, c, L, s, M, s.x2, s.x, n2_ready, l + 1 < c.llm_layers ? w->layers[l + 1].ln1 : nullptr, &n1_ready));
@@ -640,7 +615,7 @@ static int32_t prefill_chunk_impl(void* stream, const uvx_config_t* cfg, const u
   UVX_CHECK(Tn >= 1 && cur_len >= 0 && Tf <= Tmax, UVX_ERR_SHAPE, "llm_prefill_chunk: %d cached + %d new positions exceed the cache length %d",
             cur_len, Tn, Tmax);
   UVX_CHECK(w->rope_len >= Tmax, UVX_ERR_SHAPE, "llm_prefill_chunk: rope table (%d) shorter than the cache (%d)", w->rope_len, Tmax);
-  RC(g3_check(c, w, cur_len + Tn));   // (Gemma-3 weight check; cache + chunk beyond the window run the windowed kernels)
+  RC(gemma3_check(c, w));             // (cache + chunk beyond the window run the windowed kernels)
   hipStream_t st = (hipStream_t)stream;
   Arena a(workspace, ws_bytes);
   ChunkWs k;
@@ -650,8 +625,7 @@ static int32_t prefill_chunk_impl(void* stream, const uvx_config_t* cfg, const u
   const size_t es = esz(dt);
   hipLaunchKernelGGL(chunk_positions_k, dim3(cdiv(M, 256)), dim3(256), 0, st, positions0, s.pos, B, Tn);
   UVX_LAUNCH_CHECK();
-  UVX_HIP(hipMemcpyAsync(s.x, inputs_embeds, (size_t)M * D * es, hipMemcpyDeviceToDevice, st));
-  if (c.llm_flavor == UVX_LLM_GEMMA) RC(scale_inplace(st, dt, s.x, (long long)M * D, gemma_normalizer(c)));
+  RC(embed_in(st, c, s.x, inputs_embeds, M));
   UVX_HIP(hipMemsetAsync(k.fq, 0, (size_t)B * Tf * s.QKV * es, st));   // the prefix rows' (skipped) query part stays defined
   const size_t layer_stride = (size_t)2 * B * Tmax * KVD;  // elements
   bool n1_ready = false, n2_ready = false;
@@ -671,12 +645,9 @@ static int32_t prefill_chunk_impl(void* stream, const uvx_config_t* cfg, const u
       UVX_HIP(hipMemcpy2DAsync(at(k.fq, ((size_t)b * Tf + cur_len) * s.QKV, dt), (size_t)s.QKV * es, at(s.qkv, (size_t)b * Tn * s.QKV, dt),
                                (size_t)s.QKV * es, (size_t)Hq * dh * es, Tn, hipMemcpyDeviceToDevice, st));
     if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(k.fq, (size_t)(Hq + Hkv) * dh, dt), k.fvt, B, Tf, k.Tfp, Hkv, dh, s.QKV));
-    AttnDesc ad;
-    ad.q = k.fq; ad.k = at(k.fq, (size_t)Hq * dh, dt); ad.v = at(k.fq, (size_t)(Hq + Hkv) * dh, dt);
-    ad.vt = k.fvt; ad.o = k.fo; ad.lse = nullptr; ad.kv_start = kv_start; ad.kv_len = nullptr;
-    ad.B = B; ad.T = Tf; ad.Tp = k.Tfp; ad.Hq = Hq; ad.Hkv = Hkv; ad.D = dh;
-    ad.ldq = ad.ldk = ad.ldv = s.QKV; ad.ldo = s.OD; ad.causal = 1; ad.q_begin = cur_len; ad.scale = attn_scale_of(c);
-    ad.window = c.llm_window > 0 && Tf > c.llm_window && w->layer_local && w->layer_local[l] ? c.llm_window : 0;
+    AttnDesc ad = causal_gqa_desc(c, k.fq, B, Tf, k.Tfp, s.QKV, s.OD);
+    ad.vt = k.fvt; ad.o = k.fo; ad.kv_start = kv_start; ad.q_begin = cur_len;
+    ad.window = window_of(c, w, l, Tf);
     RC(attention_fwd(st, dt, ad));
     for (int b = 0; b < B; ++b)
       UVX_HIP(hipMemcpyAsync(at(s.o, (size_t)b * Tn * s.OD, dt), at(k.fo, ((size_t)b * Tf + cur_len) * s.OD, dt), (size_t)Tn * s.OD * es,
@@ -721,10 +692,8 @@ extern "C" int32_t uvx_llm_decode(void* stream, const uvx_config_t* cfg, const u
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "llm_decode: workspace %zu < %zu bytes", ws_bytes, a.off);
   const int dt = c.dtype, D = c.llm_d, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh;
   UVX_CHECK(dh == 64 || dh == 128 || dh == 256, UVX_ERR_UNSUPPORTED, "llm_decode: head_dim %d not supported", dh);
-  RC(g3_check(c, w, 0));          // (weights / tables only: the sliding-window layers clamp their key range below)
-  const size_t es = esz(dt);
-  UVX_HIP(hipMemcpyAsync(s.x, token_embeds, (size_t)B * D * es, hipMemcpyDeviceToDevice, st));
-  if (c.llm_flavor == UVX_LLM_GEMMA) RC(scale_inplace(st, dt, s.x, (long long)B * D, gemma_normalizer(c)));
+  RC(gemma3_check(c, w));         // (weights / tables only: the sliding-window layers clamp their key range below)
+  RC(embed_in(st, c, s.x, token_embeds, B));
   const size_t layer_stride = (size_t)2 * B * Tmax * KVD;
   const float scale = attn_scale_of(c);
   bool n1_ready = false, n2_ready = false;      // batches beyond 16 rows (tiled split-K linears): the norms ride in the reduce kernels
@@ -747,9 +716,7 @@ extern "C" int32_t uvx_llm_decode(void* stream, const uvx_config_t* cfg, const u
       if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, B, D, c.rms_eps, c.llm_flavor));
       RC(qkv_rope(st, c, w, L, s.n, s.qkv, positions, B, 1, s.QKV, l, &s));
     }
-    // Gemma-3 sliding-window layer: the new token attends to the last `window` positions = cache slots (the slots of a sequence are
-    // contiguous, so the window is a clamp of the first visible slot)
-    const int lo = (c.llm_window > 0 && w->layer_local && w->layer_local[l]) ? max(0, cur_len + 1 - c.llm_window) : 0;
+    const int lo = decode_first_slot(c, w, l, cur_len);      // sliding-window layer: the new token attends to the last `window` cache slots
     char* ck = at(kv_cache, l * layer_stride, dt);
     char* cv = at(kv_cache, l * layer_stride + (size_t)B * Tmax * KVD, dt);
     const long long n = (long long)B * (KVD / 8);

@@ -1,5 +1,5 @@
-// Host-side helpers of the orchestration files (model.hip, generate.hip, wav2vec2.hip, enc_stack.hip): workspace carving, element
-// addressing, error propagation, the plain linear's GEMM descriptor.
+// Host-side helpers of the orchestration files (model.hip, llm_stack.hip, generate.hip, wav2vec2.hip, enc_stack.hip): workspace carving, element
+// addressing, error propagation, the configuration check, the plain linear's GEMM descriptor.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -29,6 +29,20 @@ inline char* at(const void* p, size_t elems, int dtype) { return (char*)p + elem
     int _rc = (expr);       \
     if (_rc) return _rc;    \
   } while (0)
+
+inline int check_cfg(const uvx_config_t* c) {
+  UVX_CHECK(c != nullptr, UVX_ERR_INVALID, "null config");
+  UVX_CHECK(c->dtype == DT_BF16 || c->dtype == DT_F32, UVX_ERR_INVALID, "bad dtype %d", c->dtype);
+  UVX_CHECK(c->llm_flavor >= UVX_LLM_LLAMA && c->llm_flavor <= UVX_LLM_GEMMA3, UVX_ERR_INVALID, "bad llm_flavor %d", c->llm_flavor);
+  UVX_CHECK(c->llm_act >= UVX_ACT_SILU && c->llm_act <= UVX_ACT_GELU_ERF && (c->llm_flavor != UVX_LLM_LLAMA) == (c->llm_act != UVX_ACT_SILU),
+            UVX_ERR_INVALID, "llm_act %d does not fit llm_flavor %d (Llama: SiLU; Gemma: tanh- or erf-GELU)", c->llm_act, c->llm_flavor);
+  UVX_CHECK(c->llm_wt_stream == 0 || c->llm_wt_stream == 1, UVX_ERR_INVALID, "llm_wt_stream %d: 0 or 1", c->llm_wt_stream);
+  UVX_CHECK(c->llm_qk_norm == 0 || (c->llm_qk_norm == 1 && c->llm_flavor != UVX_LLM_GEMMA), UVX_ERR_INVALID,
+            "llm_qk_norm %d: 0 or 1 (Qwen3: Llama-flavoured; Gemma-3: Gemma-flavoured)", c->llm_qk_norm);
+  UVX_CHECK((c->llm_flavor == UVX_LLM_GEMMA3) == (c->llm_qk_norm == 1 && c->llm_flavor == UVX_LLM_GEMMA3) && c->llm_attn_scale >= 0.f &&
+            c->llm_window >= 0, UVX_ERR_INVALID, "Gemma-3 needs llm_qk_norm = 1; llm_attn_scale / llm_window must not be negative");
+  return UVX_OK;
+}
 
 // y [M, N] = x [M, K] . W [N, K]^T
 inline GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) {

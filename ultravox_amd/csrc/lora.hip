@@ -512,7 +512,7 @@ int lora_transpose(hipStream_t st, int dtype, const void* in, void* out, int C, 
   return UVX_OK;
 }
 
-// ---- whole adapted linears: what the towers' training paths (enc_stack.hip, model.hip) call per projection ----
+// ---- whole adapted linears: what the towers' training paths (enc_stack.hip, llm_stack.hip) call per projection ----
 #define UVX_LORA_RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 // One adapted linear (peft Linear.forward, dropout 0): y[M, cout] += round(scale * (x A^T) B^T).  t [M, 64 of a 128-column row] keeps
 // x A^T and bT [r, cout] the transposed lora_B for the backward.

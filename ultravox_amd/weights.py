@@ -371,14 +371,14 @@ def pack_encoder(sd, cfg: UltravoxConfig, dtype, device, prefix="audio_tower.", 
 
 def pack_llm(sd, cfg: UltravoxConfig, dtype, device, with_transposes: bool = True, rope_len: Optional[int] = None,
              prefix="language_model.", consume: bool = False) -> Dict[str, object]:
-    """HF-named LLM weights -> the packed per-layer operands of csrc/model.hip.  q/k/v and gate/up are concatenated (new
+    """HF-named LLM weights -> the packed per-layer operands of csrc/llm_stack.hip.  q/k/v and gate/up are concatenated (new
     tensors); the other matrices are shared with `sd` when they already have the right device / dtype.  `consume=True` pops
     the q/k/v/gate/up entries from `sd` layer by layer as soon as they are packed, so the peak stays at one copy of the model
     plus one layer (what a 70B-parameter LLM needs to load into 288 GB next to its KV cache) — `sd` is left without them."""
     t = cfg.text_config
     cv = lambda x: x.to(device=device, dtype=dtype).contiguous()
     # with_transposes: True = a resident W^T per frozen linear + lm_head^T (the NT dgrads), False = none (inference, or the streamed copies),
-    # "head" = lm_head^T only: the layers' dgrads then take the NN form on the forward weights (csrc/model.hip lin_dgrad; bf16, round 6)
+    # "head" = lm_head^T only: the layers' dgrads then take the NN form on the forward weights (csrc/llm_stack.hip lin_dgrad; bf16, round 6)
     tr_head = lambda x: x.t().contiguous() if with_transposes else None
     tr = lambda x: x.t().contiguous() if with_transposes is True else None
     if prefix + "model.embed_tokens.weight" not in sd and prefix + "base_model.model.model.embed_tokens.weight" in sd:
