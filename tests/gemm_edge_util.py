@@ -498,14 +498,15 @@ def _join_gu(gate, up):
 
 def ref_epilogue(g, o):
     """float64 epilogue, no rounding anywhere -> {out: (value, bar, live)}; bar = the absolute error bound of the module docstring;
-    live = the output really depends on its pre-activation (|GELU'| / |SiLU'| >= 0.25: a changed pre-activation must show there)."""
+    live = the output really depends on its pre-activation (|GELU'| / |SiLU'| >= 0.25: a changed pre-activation must show there).
+    o["e_extra"], where given: error that the operands bring along (gemm_skinny_edge_util's norm stage), carried like the accumulation's."""
     al, P = o["alpha"], o["P"]
     acc = (2.0 * math.sqrt(o["K"]) + 4.0) * EPS
     x = al * P
     s0 = abs(al) * o["absP"]
     if o["bias"] is not None:
         x, s0 = x + o["bias"], s0 + o["bias"].abs()
-    e = acc * s0
+    e = acc * s0 + o.get("e_extra", 0.0)
     yes = torch.ones_like(x, dtype=torch.bool)
     form = g["form"]
     if g["epi"] == 1:
