@@ -471,40 +471,94 @@ int32_t uvx_gemm_force_variant(int32_t variant);
  * it replaces (norm_out [M, K] is the scratch for that case, may be NULL when the fused kernel is known to apply).  lda must equal K. */
 int32_t uvx_gemm_rmsnorm(void* stream, int32_t dtype, const uvx_gemm_desc_t* g, const void* norm_w, float eps, int32_t flavor,
                          void* norm_out);
-/* probes (same-box A/B inside bench.py): key 1 = 16-byte epilogue loads/stores (default 1), key 2 = SwiGLU backward fused
- * into the down-projection dgrad GEMM (0 = separate kernel, 1 = round 2's fragment-layout epilogue (measured neutral),
- * 2 = whole-line epilogue through the LDS stage (round 3)), key 3 = LM head / CE / head dgrad on the supervised
- * rows only (default 1; must not change between uvx_llm_fwd and uvx_llm_bwd), key 4 = weight-streaming GEMM kernels for
- * few-row problems (the decode step; default 1: row-streaming kernel for M <= 2, MFMA kernel with the weights staged through LDS for
- * M = 3..64 when K % 2048 == 0, straight fragment loads for other M <= 16; 2 = straight fragment loads for every M <= 16 - round 2's
- * kernel - and the tiled kernels above, for A/B; 0 = the tiled kernels), key 5 = the streamed weight transposes (llm_wt_stream) use plain instead of
- * non-temporal loads / stores (default 0), key 11 = number of LLM layer chains: the batch
- * is cut into that many slices whose layer chains run on as many streams (default 1 = one chain on the caller's stream, at most 4; which of 1 / 2 is
- * faster depends on the box: UltravoxTrainer.autotune_schedule times both; uvx_llm_fwd* / uvx_llm_bwd*: same kernels on the same rows, bit-identical results; the side streams are
- * forked from and joined into the caller's stream by events, so the call stays stream-ordered for the caller), key 12 = bf16
- * attention kernels read V^T / Q^T / K^T / dO^T out of the natural tiles with the transposing LDS read instead of from
- * transposed copies in global memory (default 1; 0 restores the copies: heads_transpose + the *_t staging), key 13 = the fused attention backward
- * kernel for head_dim 128 / causal / at most 320 positions (default 1; 0 = the dQ + dK/dV kernel pair), key 14 = the LLM's attention backward writes dq / dk
- * RoPE-inverted from its own epilogues instead of a separate pass over d_qkv (default 1; bit-identical), key 15 = TIMING
- * PROBE ONLY (default 0): bit mask of kernel classes that are not launched (results are garbage; what the class costs inside
- * the overlapped schedule): 1 LLM attention backward, 2 LLM attention forward, 4 SwiGLU backward, 8 RMSNorm backward,
- * 16 RMSNorm forward, 32 RoPE forward, 64 encoder attention, 128 encoder LayerNorm, key 16 = the prefill's rotary embedding and KV-cache
- * append in one launch per layer (default 1; 0 = the rope + append pair; bit-identical), key 17 = a split-K linear of generate() that is
- * followed by an RMSNorm (o_proj -> post_attention_layernorm, down_proj -> the next layer's input_layernorm) has that norm computed by its
- * reduce kernel (default 1; 0 = the separate rmsnorm launch; bit-identical), key 18 = 1: the RMSNorm forward of plain rows runs the two-pass kernel
- * instead of the one that keeps the row in registers (default 0; bit-identical; A/B), key 19 = tile form of the head_dim-64 attention backward pair (the
- * Whisper tower under LoRA training): 0 = two 16-query tiles per wave in the dQ kernel (default), 1 = one tile per wave in both kernels (rounds 1-5), 2 = two in
- * both, 3 = two in the dK/dV kernel only, 4 = 64-row steps, 5 / 6 = eight-wave blocks (all bit-identical; A/B), key 20 = 1: the head_dim-64 forward kernel takes
- * its row max through ds_bpermute shuffles instead of v_permlane swaps (default 0; bit-identical; A/B), key 21 = 1: the training tower's GELU and GELU backward
- * run as separate kernels instead of in the fc1 / fc2-dgrad GEMM epilogues (uvx_gemm_desc_t.act 2 / 3; default 0; bit-identical; A/B), key 23 = 1: the decode step's rotary embedding and
- * KV-cache append of the new token run as their own launch per layer instead of inside the grouped decode-attention kernel (default 0; bit-identical; A/B)., key 22 = 1: the training tower's q_proj / k_proj adapter products run as
- * separate launches instead of paired ones (lora_down2 / lora_up2 / one partial-sum launch for the four weight gradients; default 0; bit-identical; A/B),
- * key 24 = 1: uvx_gemm_rmsnorm / the decode step at 3..16 rows (K % 2048 == 0) normalise the activation fragments inside the staged weight-streaming
- * kernel instead of running rmsnorm + linear as two launches (default 0: measured 19-32 % slower per token; same arithmetic and rounding points, rstd may
- * differ in the last bit; A/B), key 25: the head_dim-128 causal attention forward under grouped-query attention (Hq / Hkv a multiple of 4, T <= 512) - 0 (default):
- * blocks whose four waves take four query heads of one KV head when the launch has >= 512 of them, 5: never, 1 / 3 / 4: always, with two / three / one
- * query tiles per wave (bit-identical in every form; A/B), key 26: weight rows in flight per wave of the one-row decode GEMV - 0 (default): 2, 4 / 8 / 16: that many
- * (agree to rounding, not bitwise; A/B). */
+/* Tuning options: the keys of uvx_set_option / uvx_get_option (probes and same-box A/B inside bench.py; the product sets only
+ * UVX_OPT_LLM_CHAINS and UVX_OPT_ATTN_BWD_FUSED, from UltravoxTrainer.autotune_schedule).  Each key keeps its number for good.  Keys 27 .. 31 are
+ * unassigned: uvx_set_option stores them and nothing reads them.  Key 0 and keys >= 32 are rejected. */
+typedef enum {
+  /* access width of the bf16 GEMM epilogue: 0 = 8-byte loads / stores in the fragment layout, 1 = 16 bytes via v_permlane16_swap
+   * (-0.5 ms/step at C2), 2 = row-contiguous through LDS.  Default 2. */
+  UVX_OPT_EPILOGUE_IO = 1,
+  /* SwiGLU backward fused into the down-projection dgrad GEMM: 0 = separate kernel, 1 = round 2's fragment-layout epilogue (measured
+   * neutral at C2 - the separate elementwise kernel runs at 6.7 TB/s, the fused epilogue is serialised behind each tile's main loop),
+   * 2 = whole-line epilogue through the LDS stage (round 3).  Default 0. */
+  UVX_OPT_SWIGLU_BWD_IN_DGRAD = 2,
+  /* LM head / CE / head dgrad on the supervised rows only: 1 = on, 0 = every row.  Default 1; must not change between uvx_llm_fwd and
+   * uvx_llm_bwd. */
+  UVX_OPT_LOSS_HEAD_SUPERVISED_ROWS = 3,
+  /* weight-streaming GEMM kernels for few-row problems (the decode step): 1 = row-streaming kernel for M <= 2, MFMA kernel with the
+   * weights staged through LDS for M = 3..64 when K % 2048 == 0, straight fragment loads for other M <= 16; 2 = straight fragment loads
+   * for every M <= 16 - round 2's kernel - and the tiled kernels above, for A/B; 0 = the tiled kernels.  Default 1. */
+  UVX_OPT_SKINNY_GEMM = 4,
+  /* 1 = the streamed weight transposes (llm_wt_stream) use plain instead of non-temporal loads / stores.  Default 0; A/B. */
+  UVX_OPT_WT_STREAM_PLAIN_ACCESS = 5,
+  /* the tile picker uses the merged-phase kernels 31..34: 1 = on, 0 = the round-1 four-phase set 11, 15..19 (A/B builds, never split).
+   * Default 1. */
+  UVX_OPT_MERGED_PHASE_TILES = 6,
+  /* m-major tile order when the activation matrix is the larger operand (M > N: the encoder's GEMMs): 1 = on, 0 = off.  Default 1. */
+  UVX_OPT_M_MAJOR_TILES = 7,
+  /* (probe builds) 1 = let the picker choose the stream-K variants 39..42.  Default 0: measured slower, see the kernel. */
+  UVX_OPT_STREAMK_PICK = 8,
+  /* stream-K flavour, data-parallel rounds before the stream-K part: 1 = all but the last full round ("two-tile"), 0 = none.
+   * Default 1. */
+  UVX_OPT_STREAMK_TWO_TILE = 9,
+  /* tail-split threshold in per cent of the whole launch's modelled cost.  Default 0 = 88. */
+  UVX_OPT_TAIL_SPLIT_PCT = 10,
+  /* number of LLM layer chains: the batch is cut into that many slices whose layer chains run on as many streams (1 = one chain on the
+   * caller's stream, at most 4; which of 1 / 2 is faster depends on the box: UltravoxTrainer.autotune_schedule times both;
+   * uvx_llm_fwd* / uvx_llm_bwd*: same kernels on the same rows, bit-identical results; the side streams are forked from and joined into
+   * the caller's stream by events, so the call stays stream-ordered for the caller).  Default 1. */
+  UVX_OPT_LLM_CHAINS = 11,
+  /* bf16 attention kernels read V^T / Q^T / K^T / dO^T out of the natural tiles with the transposing LDS read instead of from
+   * transposed copies in global memory: 1 = on, 0 restores the copies (heads_transpose + the *_t staging).  Default 1. */
+  UVX_OPT_ATTN_TR_READS = 12,
+  /* the fused attention backward kernel for head_dim 128 / causal / at most 320 positions: 1 = on, 0 = the dQ + dK/dV kernel pair (sums
+   * in another order: agrees to rounding, not bitwise).  Default 1. */
+  UVX_OPT_ATTN_BWD_FUSED = 13,
+  /* the LLM's attention backward writes dq / dk RoPE-inverted from its own epilogues instead of a separate pass over d_qkv: 1 = on,
+   * 0 = the separate pass.  Default 1; bit-identical. */
+  UVX_OPT_ATTN_BWD_ROPE_FUSED = 14,
+  /* TIMING PROBE ONLY: bit mask of kernel classes that are not launched (results are garbage; what the class costs inside the
+   * overlapped schedule): 1 LLM attention backward, 2 LLM attention forward, 4 SwiGLU backward, 8 RMSNorm backward, 16 RMSNorm forward,
+   * 32 RoPE forward, 64 encoder attention, 128 encoder LayerNorm.  Default 0. */
+  UVX_OPT_PROBE_SKIP_MASK = 15,
+  /* the prefill's rotary embedding and KV-cache append in one launch per layer: 1 = on, 0 = the rope + append pair.  Default 1;
+   * bit-identical. */
+  UVX_OPT_PREFILL_ROPE_APPEND_FUSED = 16,
+  /* a split-K linear of generate() that is followed by an RMSNorm (o_proj -> post_attention_layernorm, down_proj -> the next layer's
+   * input_layernorm) has that norm computed by its reduce kernel: 1 = on, 0 = the separate rmsnorm launch.  Default 1; bit-identical. */
+  UVX_OPT_SPLITK_REDUCE_NORM = 17,
+  /* 1 = the RMSNorm forward of plain rows runs the two-pass kernel instead of the one that keeps the row in registers.  Default 0;
+   * bit-identical; A/B. */
+  UVX_OPT_RMSNORM_TWO_PASS = 18,
+  /* tile form of the head_dim-64 attention backward pair (the Whisper tower under LoRA training): 0 = two 16-query tiles per wave in the
+   * dQ kernel, 1 = one tile per wave in both kernels (rounds 1-5), 2 = two in both, 3 = two in the dK/dV kernel only, 4 = 64-row steps,
+   * 5 / 6 = eight-wave blocks.  Default 0; all bit-identical; A/B. */
+  UVX_OPT_ATTN_BWD64_FORM = 19,
+  /* 1 = the head_dim-64 forward kernel takes its row max through ds_bpermute shuffles instead of v_permlane swaps.  Default 0;
+   * bit-identical; A/B. */
+  UVX_OPT_ATTN_FWD64_BPERMUTE_MAX = 20,
+  /* 1 = the training tower's GELU and GELU backward run as separate kernels instead of in the fc1 / fc2-dgrad GEMM epilogues
+   * (uvx_gemm_desc_t.act 2 / 3).  Default 0; bit-identical; A/B. */
+  UVX_OPT_TOWER_GELU_SEPARATE = 21,
+  /* 1 = the training tower's q_proj / k_proj adapter products run as separate launches instead of paired ones (lora_down2 / lora_up2 /
+   * one partial-sum launch for the four weight gradients).  Default 0; bit-identical; A/B. */
+  UVX_OPT_LORA_QK_SEPARATE = 22,
+  /* 1 = the decode step's rotary embedding and KV-cache append of the new token run as their own launch per layer instead of inside the
+   * grouped decode-attention kernel.  Default 0; bit-identical; A/B. */
+  UVX_OPT_DECODE_ROPE_APPEND_SEPARATE = 23,
+  /* 1 = uvx_gemm_rmsnorm / the decode step at 3..16 rows (K % 2048 == 0) normalise the activation fragments inside the staged
+   * weight-streaming kernel instead of running rmsnorm + linear as two launches.  Default 0: measured 19-32 % slower per token; same
+   * arithmetic and rounding points, rstd may differ in the last bit; A/B. */
+  UVX_OPT_SKINNY_RMSNORM_STAGED = 24,
+  /* the head_dim-128 causal attention forward under grouped-query attention (Hq / Hkv a multiple of 4, T <= 512): 0 = blocks whose four
+   * waves take four query heads of one KV head when the launch has >= 512 of them, 5 = never, 1 / 3 / 4 = always, with two / three /
+   * one query tiles per wave.  Default 0; bit-identical in every form; A/B. */
+  UVX_OPT_ATTN_FWD_GQ_FORM = 25,
+  /* weight rows in flight per wave of the one-row decode GEMV: 0 = 2, 4 / 8 / 16 = that many.  Default 0; agree to rounding, not bitwise;
+   * A/B. */
+  UVX_OPT_GEMV_ROWS_IN_FLIGHT = 26
+} uvx_option_t;
+/* set a tuning option (key: a uvx_option_t; UVX_ERR_INVALID for key 0 and keys >= 32) */
 int32_t uvx_set_option(int32_t key, int32_t value);
 /* the current value of a tuning option (-1: unknown key) */
 int32_t uvx_get_option(int32_t key);

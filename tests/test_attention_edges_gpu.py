@@ -65,11 +65,8 @@ def test_bf16_attention_at_mask_and_tile_edges(c):
         _same(_run(c, q, k, v, do, kv_start, kv_len), base, f"{what} second run")
 
         if fused:                                              # the dQ + dK/dV pair where the fused backward ran: another summation order
-            L.uvx_set_option(13, 0)
-            try:
+            with _lib.option(_lib.Option.ATTN_BWD_FUSED, 0):
                 pair = _run(c, q, k, v, do, kv_start, kv_len, fwd=base)
-            finally:
-                L.uvx_set_option(13, 1)
             held(pair, "kernel pair", ("dq", "dk", "dv"))
             assert (pair["dk"][~seen] == 0).all() and (pair["dv"][~seen] == 0).all(), f"{what} kernel pair: unseen keys"
         if D == 64:
@@ -79,15 +76,9 @@ def test_bf16_attention_at_mask_and_tile_edges(c):
                     _same(_run(c, q, k, v, do, kv_start, kv_len), base, f"{what} force_qt({qt})")
                 finally:
                     L.uvx_attention_force_qt(0)
-            L.uvx_set_option(19, 1)                            # one 16-row tile per wave in the backward pair
-            try:
+            with _lib.option(_lib.Option.ATTN_BWD64_FORM, 1):     # one 16-row tile per wave in the backward pair
                 _same(_run(c, q, k, v, do, kv_start, kv_len, fwd=base), base, f"{what} option 19 = 1")
-            finally:
-                L.uvx_set_option(19, 0)
         if D == 128 and (Hq // Hkv) % 4 == 0:
             for form in (1, 5):                                # the grouped-query block form of the forward: forced, never
-                L.uvx_set_option(25, form)
-                try:
+                with _lib.option(_lib.Option.ATTN_FWD_GQ_FORM, form):
                     _same(_run(c, q, k, v, do, kv_start, kv_len), base, f"{what} option 25 = {form}")
-                finally:
-                    L.uvx_set_option(25, 0)

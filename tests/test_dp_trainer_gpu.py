@@ -194,14 +194,13 @@ def test_schedule_autotuner_picks_a_schedule_and_changes_no_result():
         tr.flush()
         return tr, losses, model.projector_state_dict()
 
-    try:
+    chains = _lib.Option.LLM_CHAINS
+    with _lib.option(chains, _lib.lib().uvx_get_option(chains)):      # the tuner leaves its verdict set: the entry value comes back at the end
         tr, losses, params = run(True)
         assert tr.llm_schedule in ({11: 1}, {11: 2}) and len(tr.schedule_timings) == 2 and tr._tune is None
         assert tr.schedule_chains == tr.llm_schedule[11]
-        _lib.lib().uvx_set_option(11, 1)
-        _, losses0, params0 = run(False)
-    finally:
-        _lib.lib().uvx_set_option(11, 1)
+        with _lib.option(chains, 1):
+            _, losses0, params0 = run(False)
     assert losses == losses0
     for k in params:
         assert torch.equal(params[k], params0[k]), k

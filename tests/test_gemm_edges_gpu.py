@@ -129,18 +129,6 @@ def _forced(c):
     return Forced()
 
 
-class _Option:
-    def __init__(self, key, value):
-        self.key, self.value = key, value
-
-    def __enter__(self):
-        self.old = _lib().lib().uvx_get_option(self.key)
-        _lib().lib().uvx_set_option(self.key, self.value)
-
-    def __exit__(self, *exc):
-        _lib().lib().uvx_set_option(self.key, self.old)
-
-
 def _group(name):
     return [c for c in CASES if c["group"] == name]
 
@@ -154,7 +142,7 @@ def _plain_group(c):
                 what = f"{case_id(c)} {form} family {fam}"
                 if form == "ep2":
                     for v in c.get("opt2", (2,)):             # the fragment-layout (1) and the staged (2) form of the SwiGLU backward
-                        with _Option(2, v):
+                        with _lib().option(_lib().Option.SWIGLU_BWD_IN_DGRAD, v):
                             _held(p, f"{what} option 2 = {v}")
                 else:
                     _held(p, what)
@@ -220,7 +208,7 @@ def test_tail_split_second_launch_offsets(form):
         p = make_problem(c, fam, DEV)
         what = f"{case_id(c)} {form} family {fam}"
         try:
-            with _Option(10, 190):
+            with _lib().option(_lib().Option.TAIL_SPLIT_PCT, 190):
                 L.uvx_gemm_force_variant(-1)
                 recs = _held(p, what + " tail split", records=True)
                 # 100 + tile 0: 128-column panels, so the cut is at 128 whole panels = column 16384, the n_main of the CPU mutation proof

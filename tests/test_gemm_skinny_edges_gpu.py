@@ -32,6 +32,7 @@ call and the path (200 / 201 / 202 / a tile) held in all 122 tests; the launch a
 static reduction arrays - is accepted (a work-group of gfx950 may take up to 160 KiB) and within its bars.  At 256 CUs N = 4 is one block of
 SIXTEEN weight rows (no balance gain from eight: the 5 % rule keeps the larger block), all clamped to row 3; 8 rows per block start at N = 12.
 """
+import contextlib
 import ctypes as C
 
 import pytest
@@ -76,23 +77,6 @@ def _records():
     n = L.uvx_prof_records(buf, 16)
     L.uvx_prof_end(tot, 3)
     return [tuple(int(buf[i * 6 + j]) for j in range(5)) for i in range(n)]
-
-
-class _Options:
-    """tuning options for the length of a `with`; the old values come back whatever happens inside"""
-
-    def __init__(self, **kv):
-        self.kv = {int(k[1:]): v for k, v in kv.items() if v is not None}
-
-    def __enter__(self):
-        L = _lib().lib()
-        self.old = {k: L.uvx_get_option(k) for k in self.kv}
-        for k, v in self.kv.items():
-            L.uvx_set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            _lib().lib().uvx_set_option(k, v)
 
 
 def _launch(p, norm_out=None):
@@ -169,7 +153,11 @@ def _run(c, second=None):
     """every form and family of a case under its options; the record says which entry served it -> nothing"""
     c = _for_device(c)
     o4, o24, o26 = c.get("opt4", 1), c.get("opt24", 0), c.get("opt26")
-    with _Options(o4=o4, o24=o24, o26=o26):
+    O = _lib().Option
+    with contextlib.ExitStack() as options:      # the old values come back whatever happens inside
+        for key, v in ((O.SKINNY_GEMM, o4), (O.SKINNY_RMSNORM_STAGED, o24), (O.GEMV_ROWS_IN_FLIGHT, o26)):
+            if v is not None:
+                options.enter_context(_lib().option(key, v))
         for form in c["forms"]:
             cf = with_form(c, form)
             sw = form == "ep1"
@@ -239,7 +227,7 @@ def _two_launches(p, what):
     g, outs = p.g, p.outputs()
     first = {k: p.buf[k].clone() for k in outs}
     norm_out = torch.empty(g["M"] * g["K"], device=DEV, dtype=torch.bfloat16)
-    with _Options(o24=0):
+    with L.option(L.Option.SKINNY_RMSNORM_STAGED, 0):
         L.lib().uvx_prof_begin()
         try:
             _launch(p, norm_out)

@@ -410,9 +410,8 @@ def test_prefill_rope_and_cache_append_in_one_launch_is_bit_identical(family):
     ids[am == 0] = 2
     L = _lib.lib()
     runs = []
-    try:
-        for opt in (1, 0):
-            L.uvx_set_option(16, opt)
+    for opt in (1, 0):
+        with _lib.option(_lib.Option.PREFILL_ROPE_APPEND_FUSED, opt):
             out = model.generate(ids.to(DEV), attention_mask=am.to(DEV), max_new_tokens=new, eos_token_id=-1, return_dict_in_generate=True,
                                  output_logits=True)
             def rows(state):      # the cache rows written so far ([L][2][B][Tmax][kv_heads * head_dim]; rows >= cur_len were never written)
@@ -422,8 +421,6 @@ def test_prefill_rope_and_cache_append_in_one_launch_is_bit_identical(family):
             more = model.forward(input_ids=torch.randint(3, 512, (B, 5), generator=torch.Generator().manual_seed(5)).to(DEV),
                                  past_key_values=out.past_key_values)      # chunked prefill: five new positions per sequence
             runs.append((out.sequences, torch.stack(out.logits), cache, more.logits, rows(more.past_key_values)))
-    finally:
-        L.uvx_set_option(16, 1)
     assert L.uvx_get_option(16) == 1
     for a, b in zip(*runs):
         assert torch.equal(a, b)
@@ -464,9 +461,8 @@ def test_rmsnorm_inside_the_splitk_reduce_is_bit_identical(family):
     ids[am == 0] = 2
     more_ids = torch.randint(3, 2048, (B, 5), generator=torch.Generator().manual_seed(6)).to(DEV)
     runs = []
-    try:
-        for opt in (1, 0):
-            L.uvx_set_option(17, opt)
+    for opt in (1, 0):
+        with _lib.option(_lib.Option.SPLITK_REDUCE_NORM, opt):
             out = model.generate(ids.to(DEV), attention_mask=am.to(DEV), max_new_tokens=new, eos_token_id=-1, return_dict_in_generate=True,
                                  output_logits=True)
             st = out.past_key_values
@@ -475,8 +471,6 @@ def test_rmsnorm_inside_the_splitk_reduce_is_bit_identical(family):
             cache = rows(st)
             more = model.forward(input_ids=more_ids, past_key_values=st)      # chunked prefill: 100 rows
             runs.append((out.sequences, torch.stack(out.logits), cache, more.logits, rows(more.past_key_values)))
-    finally:
-        L.uvx_set_option(17, 1)
     for a, b in zip(*runs):
         assert torch.equal(a, b)
     assert torch.isfinite(runs[0][1].float()).all()
@@ -520,7 +514,6 @@ def test_rope_and_cache_append_inside_the_decode_attention_is_bit_identical(head
     from ultravox_amd.config import UltravoxConfig
     from ultravox_amd.model import UltravoxModel
     from ultravox_amd.weights import random_state_dict
-    L = _lib.lib()
     small = dict(SMALL)
     small["text_config"] = dict(small["text_config"], num_attention_heads=heads, num_key_value_heads=kv_heads, head_dim=head_dim,
                                 hidden_size=heads * head_dim if heads * head_dim >= 256 else 256)
@@ -532,9 +525,8 @@ def test_rope_and_cache_append_inside_the_decode_attention_is_bit_identical(head
     am = torch.ones(3, 21, dtype=torch.long)
     am[1, :5] = 0
     res = []
-    try:
-        for opt in (1, 0):
-            L.uvx_set_option(23, opt)
+    for opt in (1, 0):
+        with _lib.option(_lib.Option.DECODE_ROPE_APPEND_SEPARATE, opt):
             out = model.generate(ids, attention_mask=am.to(DEV), max_new_tokens=9, eos_token_id=-1, return_dict_in_generate=True, output_logits=True)
             torch.cuda.synchronize()
             st = out.past_key_values
@@ -542,8 +534,6 @@ def test_rope_and_cache_append_inside_the_decode_attention_is_bit_identical(head
             planes = t.num_hidden_layers * 2 * 3
             rows = st.cache.view(torch.bfloat16)[:planes * st.Tmax * kv_heads * head_dim].view(planes, st.Tmax, kv_heads * head_dim)[:, :st.cur_len]
             res.append((out.sequences.clone(), [x.clone() for x in out.logits], rows.clone(), st.cur_len))      # (rows beyond cur_len are never written)
-    finally:
-        L.uvx_set_option(23, 0)
     (s0, l0, c0, n0), (s1, l1, c1, n1) = res
     assert torch.equal(s0, s1) and n0 == n1
     for a, b in zip(l0, l1):
@@ -575,15 +565,11 @@ def test_decode_rmsnorm_inside_the_staged_skinny_kernel(B, family):
     for r in range(1, B, 2):
         am[r, :r + 2] = 0
     ids[am == 0] = 2
-    L = _lib.lib()
     runs = []
-    try:
-        for opt in (1, 0):
-            L.uvx_set_option(24, opt)
+    for opt in (1, 0):
+        with _lib.option(_lib.Option.SKINNY_RMSNORM_STAGED, opt):
             runs.append(model.generate(ids.to(DEV), attention_mask=am.to(DEV), max_new_tokens=new, eos_token_id=-1, return_dict_in_generate=True,
                                        output_logits=True))
-    finally:
-        L.uvx_set_option(24, 0)
     fused, two = runs
     for step in range(new):
         a, b = fused.logits[step].float(), two.logits[step].float()

@@ -503,31 +503,22 @@ def test_gemm_few_rows_weight_streaming_kernel(M, N, K):
     b = (torch.randn(N, K, device=DEV, generator=g) * 0.1).bfloat16()
     bias = torch.randn(N, device=DEV, generator=g).bfloat16()
     resid = torch.randn(M, N, device=DEV, generator=g).bfloat16()
-    L = _lib.lib()
+    skinny = _lib.Option.SKINNY_GEMM
     out = ops().gemm(a, b, bias=bias, residual=resid, act="gelu")
-    L.uvx_set_option(4, 0)
-    try:
+    with _lib.option(skinny, 0):
         tiled = ops().gemm(a, b, bias=bias, residual=resid, act="gelu")
         plain_tiled = ops().gemm(a, b)
-    finally:
-        L.uvx_set_option(4, 1)
     ref = F.gelu((a.float() @ b.float().t() + bias.float()).bfloat16().float()).bfloat16().float() + resid.float()
     assert rel_l2(out, ref) < 5e-3 and rel_l2(out, tiled) < 5e-3
     assert rel_l2(ops().gemm(a, b), plain_tiled) < 3e-3
-    L.uvx_set_option(4, 2)          # the MFMA mapping for every M <= 16
-    try:
+    with _lib.option(skinny, 2):    # the MFMA mapping for every M <= 16
         assert rel_l2(out, ops().gemm(a, b, bias=bias, residual=resid, act="gelu")) < 5e-3
-    finally:
-        L.uvx_set_option(4, 1)
     if N % 32 == 0:     # fused SwiGLU epilogue (interleaved gate / up packing)
         act = torch.empty(M, N // 2, device=DEV, dtype=torch.bfloat16)
         gu = ops().gemm(a, b, epilogue=1, c2=act)
-        L.uvx_set_option(4, 0)
-        try:
+        with _lib.option(skinny, 0):
             act_t = torch.empty_like(act)
             gu_t = ops().gemm(a, b, epilogue=1, c2=act_t)
-        finally:
-            L.uvx_set_option(4, 1)
         assert rel_l2(gu, gu_t) < 3e-3 and rel_l2(act, act_t) < 6e-3
 
 
@@ -541,11 +532,8 @@ def test_gemm_with_fused_rmsnorm_matches_the_two_launches(M, N, K, flavor, swigl
     as two launches: the same rounding points, so the outputs agree to the last-bit noise of a differently ordered sum of squares (rel-L2 <
     2e-3, almost every element identical); other shapes (K = 3072) take the two-launch fallback inside the entry point."""
     from ultravox_amd import _lib
-    _lib.lib().uvx_set_option(24, 1)
-    try:
+    with _lib.option(_lib.Option.SKINNY_RMSNORM_STAGED, 1):
         _fused_rmsnorm_case(M, N, K, flavor, swiglu)
-    finally:
-        _lib.lib().uvx_set_option(24, 0)
 
 
 def _fused_rmsnorm_case(M, N, K, flavor, swiglu):
@@ -585,14 +573,10 @@ def test_fused_rmsnorm_at_3_to_16_rows_is_opt_in():
     b = (torch.randn(6144, 4096, device=DEV, generator=g) * 0.05).bfloat16()
     want = ops().gemm(ops().rmsnorm(a, w, eps=1e-5), b)
     from ultravox_amd import _lib
-    L = _lib.lib()
     got = ops().gemm_rmsnorm(a, w, b, eps=1e-5)
     assert torch.equal(got, want)
-    L.uvx_set_option(24, 1)
-    try:
+    with _lib.option(_lib.Option.SKINNY_RMSNORM_STAGED, 1):
         fused = ops().gemm_rmsnorm(a, w, b, eps=1e-5)
-    finally:
-        L.uvx_set_option(24, 0)
     assert rel_l2(fused, want) < 2e-3 and (fused == want).float().mean().item() > 0.9
 
 
@@ -813,16 +797,10 @@ def test_attention_transposing_lds_reads_equal_the_transposed_copies(D, Hq, Hkv,
         o, lse = ops().attention(q, k, v, causal=causal, block=block, kv_len=kv_len)
         return (o, lse) + tuple(ops().attention_bwd(q, k, v, o, lse, do, causal=causal, block=block, kv_len=kv_len))
 
-    _lib.lib().uvx_set_option(13, 0)          # the kernel PAIR on both sides (the fused backward sums in another order)
-    try:
+    with _lib.option(_lib.Option.ATTN_BWD_FUSED, 0):      # the kernel PAIR on both sides (the fused backward sums in another order)
         new = run()
-        _lib.lib().uvx_set_option(12, 0)
-        try:
+        with _lib.option(_lib.Option.ATTN_TR_READS, 0):
             old = run()
-        finally:
-            _lib.lib().uvx_set_option(12, 1)
-    finally:
-        _lib.lib().uvx_set_option(13, 1)
     for a, b in zip(new, old):
         assert torch.equal(a, b)
 
@@ -846,11 +824,8 @@ def test_fused_attention_backward_matches_reference_and_the_kernel_pair(T, Hq, H
     fused = ops().attention_bwd(q, k, v, o, lse, do, causal=True, kv_start=kv_start, kv_len=kv_len)
     again = ops().attention_bwd(q, k, v, o, lse, do, causal=True, kv_start=kv_start, kv_len=kv_len)
     assert all(torch.equal(a, b) for a, b in zip(fused, again))
-    _lib.lib().uvx_set_option(13, 0)
-    try:
+    with _lib.option(_lib.Option.ATTN_BWD_FUSED, 0):
         pair = ops().attention_bwd(q, k, v, o, lse, do, causal=True, kv_start=kv_start, kv_len=kv_len)
-    finally:
-        _lib.lib().uvx_set_option(13, 1)
     qr, kr, vr = (t.float().requires_grad_(True) for t in (q, k, v))
     ref, ok = sdpa_ref(qr, kr, vr, True, 0, D ** -0.5, kv_start=kv_start, kv_len=kv_len)
     valid = ok.any(-1)[:, 0]
@@ -874,17 +849,13 @@ def test_rmsnorm_forward_with_the_row_in_registers_is_bit_identical(rows, cols):
     and block summation order, arithmetic and rounding points as the two-pass kernel (option 18 = 1): bit-identical outputs, and the
     bf16-vs-torch check of the rounding-points test still holds for it."""
     from ultravox_amd import _lib, ops
-    L = _lib.lib()
     torch.manual_seed(rows + cols)
     x = (torch.randn(rows, cols, device=DEV) * 1.7).bfloat16()
     w = (1.0 + 0.2 * torch.randn(cols, device=DEV)).bfloat16()
-    try:
-        L.uvx_set_option(18, 0)
+    with _lib.option(_lib.Option.RMSNORM_TWO_PASS, 0):
         a = ops.rmsnorm(x, w, 1e-5)
-        L.uvx_set_option(18, 1)
+    with _lib.option(_lib.Option.RMSNORM_TWO_PASS, 1):
         b = ops.rmsnorm(x, w, 1e-5)
-    finally:
-        L.uvx_set_option(18, 0)
     assert torch.equal(a, b)
     xf = x.float()
     want = w.float() * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5)).bfloat16().float()
@@ -897,7 +868,7 @@ def test_head_dim_64_attention_tile_forms_are_bit_identical(Hq, Hkv, T, causal, 
     one-tile form, 2..6 = both kernels / 64-row-step / 8-wave forms kept for A/B) and the forward row max through v_permlane swaps
     (option 20: 1 = the ds_bpermute shuffles).  Every output element sums the same terms in the same order in every form."""
     from ultravox_amd import _lib
-    L = _lib.lib()
+    O = _lib.Option
     torch.manual_seed(23)
     B, D = 2, 64
     q = bf(torch.randn(B, T, Hq, D, device=DEV))
@@ -905,22 +876,18 @@ def test_head_dim_64_attention_tile_forms_are_bit_identical(Hq, Hkv, T, causal, 
     v = bf(torch.randn(B, T, Hkv, D, device=DEV))
     do = bf(torch.randn(B, T, Hq * D, device=DEV))
     kv_len = torch.tensor([T, max(1, T - 37)], device=DEV, dtype=torch.int32) if not causal else None
-    try:
-        L.uvx_set_option(20, 1)
+    with _lib.option(O.ATTN_FWD64_BPERMUTE_MAX, 1):
         o0, lse0 = ops().attention(q, k, v, causal=causal, block=block, kv_len=kv_len)
-        L.uvx_set_option(20, 0)
+    with _lib.option(O.ATTN_FWD64_BPERMUTE_MAX, 0):
         o, lse = ops().attention(q, k, v, causal=causal, block=block, kv_len=kv_len)
         assert torch.equal(o, o0) and torch.equal(lse, lse0)
-        L.uvx_set_option(19, 1)
-        want = ops().attention_bwd(q, k, v, o, lse, do, causal=causal, block=block, kv_len=kv_len)
+        with _lib.option(O.ATTN_BWD64_FORM, 1):
+            want = ops().attention_bwd(q, k, v, o, lse, do, causal=causal, block=block, kv_len=kv_len)
         for form in (0, 2, 3, 4, 5, 6):
-            L.uvx_set_option(19, form)
-            got = ops().attention_bwd(q, k, v, o, lse, do, causal=causal, block=block, kv_len=kv_len)
+            with _lib.option(O.ATTN_BWD64_FORM, form):
+                got = ops().attention_bwd(q, k, v, o, lse, do, causal=causal, block=block, kv_len=kv_len)
             for a, b, name in zip(got, want, ("dq", "dk", "dv")):
                 assert torch.equal(a, b), (form, name)
-    finally:
-        L.uvx_set_option(19, 0)
-        L.uvx_set_option(20, 0)
 
 
 @pytest.mark.parametrize("M,N,K", [(1504, 2048, 1024), (12000, 4096, 1024), (300, 1024, 4096), (100, 132, 192), (37, 8, 64), (515, 1000, 128)])
@@ -1027,7 +994,6 @@ def test_attention_forward_grouped_query_block_form_is_bit_identical(B, Hq, Hkv,
     """attn_fwd_k<128, .., GQ> (tuning option 25): the four waves of a block take four query heads of ONE KV head - per (head, query row) the key tiles arrive
     in the same order as in the default form, so o and the log-sum-exp agree bit for bit, with padding on either side, in every tile count."""
     from ultravox_amd import _lib, ops
-    L = _lib.lib()
     torch.manual_seed(B * 1000 + T)
     qkv = torch.randn(B, T, (Hq + 2 * Hkv) * D, device=DEV).bfloat16()
     q = qkv[..., :Hq * D].view(B, T, Hq, D)
@@ -1036,12 +1002,9 @@ def test_attention_forward_grouped_query_block_form_is_bit_identical(B, Hq, Hkv,
     kv_start = torch.zeros(B, dtype=torch.int32, device=DEV)
     kv_len = torch.full((B,), T, dtype=torch.int32, device=DEV)
     kv_start[0], kv_len[B - 1] = 5, T - 9
-    try:
-        L.uvx_set_option(25, 5)
+    with _lib.option(_lib.Option.ATTN_FWD_GQ_FORM, 5):
         o_ref, lse_ref = ops.attention(q, k, v, causal=True, kv_start=kv_start, kv_len=kv_len)
-        for form in (0, 1, 3, 4):
-            L.uvx_set_option(25, form)
+    for form in (0, 1, 3, 4):
+        with _lib.option(_lib.Option.ATTN_FWD_GQ_FORM, form):
             o, lse = ops.attention(q, k, v, causal=True, kv_start=kv_start, kv_len=kv_len)
-            assert torch.equal(o, o_ref) and torch.equal(lse, lse_ref), form
-    finally:
-        L.uvx_set_option(25, 0)
+        assert torch.equal(o, o_ref) and torch.equal(lse, lse_ref), form

@@ -187,16 +187,12 @@ def test_kl_rows_step_with_the_compact_last_layer_matches_the_full_row_one(side_
     mel = WhisperFeatureExtractor(cfg.audio_config.num_mel_bins).logmel_device(pcm.to(DEV)).bfloat16()
     gb = {k: v.to(DEV) for k, v in b.items()}
     model.train()
-    L = _lib.lib()
     runs = []
-    try:
-        for opt in (1, 0, 1):
-            L.uvx_set_option(3, opt)
+    for opt in (1, 0, 1):
+        with _lib.option(_lib.Option.LOSS_HEAD_SUPERVISED_ROWS, opt):
             loss = model.forward_backward(audio_values=mel, **gb)
             assert model._llm_top_rows == bool(opt)
             runs.append((loss.clone(), model.proj_grad.clone()))
-    finally:
-        L.uvx_set_option(3, 1)
     torch.cuda.synchronize()
     (l1, g1), (l0, g0), (l2, g2) = runs
     assert torch.equal(l1, l2) and torch.equal(g1, g2)                     # the compact step is reproducible bit for bit

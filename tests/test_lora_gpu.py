@@ -274,7 +274,6 @@ def test_gelu_epilogues_and_paired_adapter_launches_are_bit_identical_to_the_sep
     separate gelu_* launches of rounds 3-5 (option 21 = 1): same loss and the same projector + adapter gradients, bit for bit (the epilogues
     restate the kernels' arithmetic and rounding points)."""
     from ultravox_amd import _lib
-    L = _lib.lib()
     cfg, sd, model, oracle, gb, ob, mel = _setup(torch.bfloat16, r=r)
     model.train()
 
@@ -283,21 +282,17 @@ def test_gelu_epilogues_and_paired_adapter_launches_are_bit_identical_to_the_sep
         torch.cuda.synchronize()
         return loss.clone(), {k: v.clone() for k, v in model.projector_grads().items()}
 
-    try:
-        L.uvx_set_option(21, 1)
-        L.uvx_set_option(22, 1)      # (and the q_proj / k_proj adapter products as separate launches: option 22 = 1; paired by default)
+    O = _lib.Option
+    # (and the q_proj / k_proj adapter products as separate launches: option 22 = 1; paired by default)
+    with _lib.option(O.TOWER_GELU_SEPARATE, 1), _lib.option(O.LORA_QK_SEPARATE, 1):
         loss0, g0 = run()
-        for o21 in (0, 1, 0):
-            L.uvx_set_option(21, o21)
-            L.uvx_set_option(22, o21)
+    for o21 in (0, 1, 0):
+        with _lib.option(O.TOWER_GELU_SEPARATE, o21), _lib.option(O.LORA_QK_SEPARATE, o21):
             loss, g = run()
             assert torch.equal(loss, loss0), o21
             for k in g0:      # (every gradient, the RMSNorm weights' included: their block partials are summed in a fixed order since round 6)
                 assert torch.equal(g[k], g0[k]), (o21, k, (g[k] != g0[k]).sum().item())
-        assert sum(v.abs().sum().item() for v in g0.values()) > 0
-    finally:
-        L.uvx_set_option(21, 0)
-        L.uvx_set_option(22, 0)
+    assert sum(v.abs().sum().item() for v in g0.values()) > 0
 
 
 def test_llm_only_training_builds_the_language_model_alone(tmp_path):

@@ -342,12 +342,9 @@ def test_loss_head_on_supervised_rows_split_k(T, first_label):
     assert abs(out.loss.item() - loss.item()) < 2e-2 * loss.item()
     assert rel_l2(d, e.grad) < 6e-2
     # the same step with the full-logits head (option 3 off) agrees to bf16 round-off of one dgrad
-    _lib.lib().uvx_set_option(3, 0)
-    try:
+    with _lib.option(_lib.Option.LOSS_HEAD_SUPERVISED_ROWS, 0):
         out2 = model.language_model_forward(emb.to(DEV), labels=labels.to(DEV), want_logits=False, save_for_bwd=True)
         d2 = model.language_model_backward(1.0)
-    finally:
-        _lib.lib().uvx_set_option(3, 1)
     assert abs(out2.loss.item() - out.loss.item()) < 1e-6 * out.loss.item()   # same per-row losses; the f32 row sum groups differently
     assert rel_l2(d, d2) < 5e-3
     # ... and so does the plain uvx_llm_fwd / uvx_llm_bwd pair (supervised-rows head, but the last layer on every row):
@@ -393,19 +390,15 @@ def test_two_stream_llm_schedule_is_bit_identical(B, T):
         torch.cuda.synchronize()
         return full.logits.clone(), full.loss.clone(), d_full, tr.loss.clone(), d_tr
 
-    L = _lib.lib()
-    try:
-        L.uvx_set_option(11, 1)
+    with _lib.option(_lib.Option.LLM_CHAINS, 1):
         one = run()
-        L.uvx_set_option(11, 2)
+    with _lib.option(_lib.Option.LLM_CHAINS, 2):
         two = run()
         two_again = run()
-        more = []
-        for n in (3, 4):                           # three / four chains (B = 2: capped at two; B = 5: slices of 2, 1, 1, 1)
-            L.uvx_set_option(11, n)
+    more = []
+    for n in (3, 4):                               # three / four chains (B = 2: capped at two; B = 5: slices of 2, 1, 1, 1)
+        with _lib.option(_lib.Option.LLM_CHAINS, n):
             more.append(run())
-    finally:
-        L.uvx_set_option(11, 1)                    # the default
     for i, a in enumerate(one):
         for other in (two, two_again, *more):
             assert torch.equal(a, other[i])
@@ -444,16 +437,12 @@ def test_llm_chains_are_bit_identical_with_extra_stash_fields(family):
         torch.cuda.synchronize()
         return out.loss.clone(), out.logits.clone(), d
 
-    L = _lib.lib()
-    try:
-        L.uvx_set_option(11, 1)
+    with _lib.option(_lib.Option.LLM_CHAINS, 1):
         one = run()
-        more = []
-        for n in (2, 3):
-            L.uvx_set_option(11, n)
+    more = []
+    for n in (2, 3):
+        with _lib.option(_lib.Option.LLM_CHAINS, n):
             more.append(run())
-    finally:
-        L.uvx_set_option(11, 1)                    # the default
     for other in more:
         for a, b in zip(one, other):
             assert torch.equal(a, b)
@@ -554,11 +543,8 @@ def test_fused_inverse_rope_in_the_attention_backward_is_bit_identical():
             return d
 
         fused = run()
-        _lib.lib().uvx_set_option(14, 0)
-        try:
+        with _lib.option(_lib.Option.ATTN_BWD_ROPE_FUSED, 0):
             separate = run()
-        finally:
-            _lib.lib().uvx_set_option(14, 1)
         assert torch.equal(fused, separate) and fused.float().abs().max() > 0
 
 

@@ -5,7 +5,9 @@ The product path FAILS LOUDLY when the HIP library is missing: there is no CPU f
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import enum
 from pathlib import Path
 
 import os
@@ -37,6 +39,49 @@ class GemmDesc(C.Structure):
 
 
 ABI_VERSION = 19  # UVX_ABI_VERSION of include/uvx.h that the struct mirrors below follow
+
+
+class Option(enum.IntEnum):
+    """The keys of uvx_set_option / uvx_get_option: uvx_option_t of include/uvx.h without the UVX_OPT_ prefix (what each key and value
+    means is written there; tests/test_options_cpu.py holds the two lists together).  A member is an int: plain numbers stay valid keys."""
+    EPILOGUE_IO = 1
+    SWIGLU_BWD_IN_DGRAD = 2
+    LOSS_HEAD_SUPERVISED_ROWS = 3
+    SKINNY_GEMM = 4
+    WT_STREAM_PLAIN_ACCESS = 5
+    MERGED_PHASE_TILES = 6
+    M_MAJOR_TILES = 7
+    STREAMK_PICK = 8
+    STREAMK_TWO_TILE = 9
+    TAIL_SPLIT_PCT = 10
+    LLM_CHAINS = 11
+    ATTN_TR_READS = 12
+    ATTN_BWD_FUSED = 13
+    ATTN_BWD_ROPE_FUSED = 14
+    PROBE_SKIP_MASK = 15
+    PREFILL_ROPE_APPEND_FUSED = 16
+    SPLITK_REDUCE_NORM = 17
+    RMSNORM_TWO_PASS = 18
+    ATTN_BWD64_FORM = 19
+    ATTN_FWD64_BPERMUTE_MAX = 20
+    TOWER_GELU_SEPARATE = 21
+    LORA_QK_SEPARATE = 22
+    DECODE_ROPE_APPEND_SEPARATE = 23
+    SKINNY_RMSNORM_STAGED = 24
+    ATTN_FWD_GQ_FORM = 25
+    GEMV_ROWS_IN_FLIGHT = 26
+
+
+@contextlib.contextmanager
+def option(key: int, value: int):
+    """Sets a tuning option for the body of a `with` and puts back the value it found, on an exception as well."""
+    l = lib()
+    old = l.uvx_get_option(int(key))
+    check(l.uvx_set_option(int(key), int(value)), "uvx_set_option")
+    try:
+        yield
+    finally:
+        l.uvx_set_option(int(key), old)
 
 
 def lib() -> C.CDLL:

@@ -4,6 +4,7 @@
 #include <string.h>
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 #include "../../include/uvx.h"
 #ifdef UVX_PROBES
 #include "../../include/uvx_probes.h"
@@ -21,28 +22,79 @@ extern "C" __attribute__((visibility("hidden"))) void uvx_set_error(const char* 
 
 extern "C" const char* uvx_last_error(void) { return g_err; }
 extern "C" int32_t uvx_abi_version(void) { return UVX_ABI_VERSION; }
-namespace uvx { extern int g_attn_qt; extern void* g_attn_tl; }
-extern "C" int32_t uvx_attention_force_qt(int32_t qt) { uvx::g_attn_qt = qt; return UVX_OK; }
+
+// ---- the process-wide tuning state (tuning.h) and its setters ----
+namespace uvx {
+namespace {
+// The default of every option key (what each key and value means: include/uvx.h, uvx_option_t).  A switch without a default label, with
+// -Wswitch an error: an enumerator added to the header without a line here does not build.
+#pragma clang diagnostic push
+#pragma clang diagnostic error "-Wswitch"
+constexpr int option_default(uvx_option_t key) {
+  switch (key) {
+    case UVX_OPT_EPILOGUE_IO:                 return 2;
+    case UVX_OPT_SWIGLU_BWD_IN_DGRAD:         return 0;
+    case UVX_OPT_LOSS_HEAD_SUPERVISED_ROWS:   return 1;
+    case UVX_OPT_SKINNY_GEMM:                 return 1;
+    case UVX_OPT_WT_STREAM_PLAIN_ACCESS:      return 0;
+    case UVX_OPT_MERGED_PHASE_TILES:          return 1;
+    case UVX_OPT_M_MAJOR_TILES:               return 1;
+    case UVX_OPT_STREAMK_PICK:                return 0;
+    case UVX_OPT_STREAMK_TWO_TILE:            return 1;
+    case UVX_OPT_TAIL_SPLIT_PCT:              return 0;   // = 88
+    case UVX_OPT_LLM_CHAINS:                  return 1;
+    case UVX_OPT_ATTN_TR_READS:               return 1;
+    case UVX_OPT_ATTN_BWD_FUSED:              return 1;
+    case UVX_OPT_ATTN_BWD_ROPE_FUSED:         return 1;
+    case UVX_OPT_PROBE_SKIP_MASK:             return 0;
+    case UVX_OPT_PREFILL_ROPE_APPEND_FUSED:   return 1;
+    case UVX_OPT_SPLITK_REDUCE_NORM:          return 1;
+    case UVX_OPT_RMSNORM_TWO_PASS:            return 0;
+    case UVX_OPT_ATTN_BWD64_FORM:             return 0;
+    case UVX_OPT_ATTN_FWD64_BPERMUTE_MAX:     return 0;
+    case UVX_OPT_TOWER_GELU_SEPARATE:         return 0;
+    case UVX_OPT_LORA_QK_SEPARATE:            return 0;
+    case UVX_OPT_DECODE_ROPE_APPEND_SEPARATE: return 0;
+    case UVX_OPT_SKINNY_RMSNORM_STAGED:       return 0;
+    case UVX_OPT_ATTN_FWD_GQ_FORM:            return 0;
+    case UVX_OPT_GEMV_ROWS_IN_FLIGHT:         return 0;
+  }
+  return 0;   // slot 0 and the unassigned keys 27 .. 31
+}
+#pragma clang diagnostic pop
+constexpr Tuning default_tuning() {
+  Tuning t = {};
+  for (int k = 0; k < kOptionSlots; ++k) t.options[k] = option_default((uvx_option_t)k);
+  t.gemm_variant = -1;   // automatic
+  t.gemm_split = 1;
+  return t;
+}
+constexpr Tuning kDefaultTuning = default_tuning();
+}  // namespace
+Tuning g_tuning = kDefaultTuning;
+}  // namespace uvx
+
+extern "C" int32_t uvx_attention_force_qt(int32_t qt) { uvx::g_tuning.attn_qt = qt; return UVX_OK; }
 #ifdef UVX_PROBES
 extern "C" int32_t uvx_probe_attn_timeline(void* stamps) {
-  uvx::g_attn_tl = stamps;
+  uvx::g_tuning.attn_tl = stamps;
   return UVX_OK;
 }
 extern "C" int32_t uvx_gemm_streamk_timeouts(void) { return uvx::gemm_streamk_timeouts(); }
 #endif
 extern "C" int32_t uvx_gemm_force_variant(int32_t v) {
-  if (v <= -2) { uvx::g_gemm_variant = -1; uvx::g_gemm_split = 0; }  // -2: automatic variant, tail split off (A/B probes)
-  else { uvx::g_gemm_variant = v; uvx::g_gemm_split = 1; }
+  if (v <= -2) { uvx::g_tuning.gemm_variant = -1; uvx::g_tuning.gemm_split = 0; }  // -2: automatic variant, tail split off (A/B probes)
+  else { uvx::g_tuning.gemm_variant = v; uvx::g_tuning.gemm_split = 1; }
   return UVX_OK;
 }
 
 extern "C" int32_t uvx_set_option(int32_t key, int32_t value) {
-  UVX_CHECK(key > 0 && key < 32, UVX_ERR_INVALID, "uvx_set_option: unknown key %d", key);
-  uvx::g_options[key] = value;
+  UVX_CHECK(key > 0 && key < uvx::kOptionSlots, UVX_ERR_INVALID, "uvx_set_option: unknown key %d", key);
+  uvx::g_tuning.options[key] = value;
   return UVX_OK;
 }
 
-extern "C" int32_t uvx_get_option(int32_t key) { return key > 0 && key < 32 ? uvx::g_options[key] : -1; }
+extern "C" int32_t uvx_get_option(int32_t key) { return key > 0 && key < uvx::kOptionSlots ? uvx::g_tuning.options[key] : -1; }
 
 extern "C" int32_t uvx_probe_lds_tr(void* stream, const int32_t* addr, int32_t* out) {
   UVX_CHECK(addr && out, UVX_ERR_INVALID, "uvx_probe_lds_tr: null argument");
@@ -52,9 +104,9 @@ extern "C" int32_t uvx_probe_lds_tr(void* stream, const int32_t* addr, int32_t* 
 extern "C" int32_t uvx_gemm_pick_variant(int32_t M, int32_t N, int32_t K, int32_t batch) { return uvx::gemm_pick_variant(M, N, K, batch); }
 
 extern "C" int32_t uvx_gemm_override_variant(int32_t M, int32_t N, int32_t K, int32_t variant) {
-  if (variant < 0) { uvx::g_gemm_ovr_n = 0; return UVX_OK; }
-  UVX_CHECK(uvx::g_gemm_ovr_n < 32, UVX_ERR_INVALID, "gemm override table full");
-  int* o = uvx::g_gemm_ovr[uvx::g_gemm_ovr_n++];
+  if (variant < 0) { uvx::g_tuning.gemm_ovr_n = 0; return UVX_OK; }
+  UVX_CHECK(uvx::g_tuning.gemm_ovr_n < uvx::kGemmOverrides, UVX_ERR_INVALID, "gemm override table full");
+  int* o = uvx::g_tuning.gemm_ovr[uvx::g_tuning.gemm_ovr_n++];
   o[0] = M; o[1] = N; o[2] = K; o[3] = variant;
   return UVX_OK;
 }

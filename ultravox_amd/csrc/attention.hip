@@ -18,6 +18,7 @@
 // same transpose kernel so that every MFMA operand is a contiguous 8/16-byte LDS read.
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace {
 
@@ -1323,12 +1324,10 @@ int check_desc(const uvx::AttnDesc& d) {
 
 namespace uvx {
 
-int g_attn_qt = 0;  // probes: force the forward kernel's q-tile count (0 = automatic)
-void* g_attn_tl = nullptr;  // probes build: stamp buffer of the fused backward kernel (uvx_probe_attn_timeline)
 // bf16 kernels read transposed operands out of the NATURAL tiles with ds_read_b64_tr_b16 (tuning option 12, default on):
 // callers then skip heads_transpose and may leave vt / qt / kt / dot null
-bool attention_tr_reads(int dtype) { return dtype == DT_BF16 && g_options[12] != 0; }
-bool attention_needs_transposed_copies(int dtype) { return dtype == DT_BF16 && g_options[12] == 0; }
+bool attention_tr_reads(int dtype) { return dtype == DT_BF16 && opt(UVX_OPT_ATTN_TR_READS) != 0; }
+bool attention_needs_transposed_copies(int dtype) { return dtype == DT_BF16 && opt(UVX_OPT_ATTN_TR_READS) == 0; }
 int attention_fwd_f32(hipStream_t st, const AttnDesc& d);
 int attention_bwd_f32(hipStream_t st, const AttnBwdDesc& d);
 
@@ -1338,11 +1337,11 @@ int attention_fwd(hipStream_t st, int dtype, const AttnDesc& d) {
   int rc = check_desc(d);
   if (rc) return rc;
   AttnArgs a = make_args(d);
-  a.tl = (unsigned long long*)g_attn_tl;
+  a.tl = (unsigned long long*)g_tuning.attn_tl;
   // q rows per block = 64 * QT.  Long sequences (the encoder's 1500 frames) want QT = 2 for K/V reuse; short
   // ones (the LLM's few hundred tokens) are latency-bound and want more, smaller blocks and fewer registers.
   // (the probe override applies to the head_dim-64 kernels only - the encoder's; the others have one or two instantiations)
-  const int qt = (uvx::g_attn_qt > 0 && d.D == 64) ? (uvx::g_attn_qt > 4 ? 4 : uvx::g_attn_qt) : (d.T >= 1024 ? 2 : 1);
+  const int qt = (uvx::g_tuning.attn_qt > 0 && d.D == 64) ? (uvx::g_tuning.attn_qt > 4 ? 4 : uvx::g_tuning.attn_qt) : (d.T >= 1024 ? 2 : 1);
   dim3 grid(d.Hq, d.B, cdiv(d.T, 4 * qt * 16));
   const bool tr = attention_tr_reads(dtype);   // V natural + transposing LDS reads (no V^T copy) - tuning option 12
   UVX_CHECK(tr ? d.v != nullptr : d.vt != nullptr, UVX_ERR_INVALID, "attention_fwd: %s is null", tr ? "v" : "vt");
@@ -1350,8 +1349,8 @@ int attention_fwd(hipStream_t st, int dtype, const AttnDesc& d) {
                         else hipLaunchKernelGGL((attn_fwd_k<DD, Q, false>), grid, dim3(256), 0, st, a); } while (0)
   if (d.D == 64) {
     // (the grouped-query form of the head_dim-128 branch below, for the LLMs with 64-wide heads - Llama-3.2-1B: 32 query / 8 KV heads; same rule, option 25)
-    const bool gq64_ok = tr && d.causal && d.block == 0 && d.T <= 512 && d.Hkv > 0 && d.Hq != d.Hkv && (d.Hq / d.Hkv) % 4 == 0 && d.q_begin == 0 && uvx::g_attn_qt == 0;
-    const int gq64 = !gq64_ok || g_options[25] == 5 ? 0 : g_options[25] ? g_options[25] : ((long long)(d.Hq / 4) * d.B * cdiv(d.T, 32) >= 512 ? 1 : 0);
+    const bool gq64_ok = tr && d.causal && d.block == 0 && d.T <= 512 && d.Hkv > 0 && d.Hq != d.Hkv && (d.Hq / d.Hkv) % 4 == 0 && d.q_begin == 0 && uvx::g_tuning.attn_qt == 0;
+    const int gq64 = !gq64_ok || opt(UVX_OPT_ATTN_FWD_GQ_FORM) == 5 ? 0 : opt(UVX_OPT_ATTN_FWD_GQ_FORM) ? opt(UVX_OPT_ATTN_FWD_GQ_FORM) : ((long long)(d.Hq / 4) * d.B * cdiv(d.T, 32) >= 512 ? 1 : 0);
     if (gq64 == 1 || gq64 == 3) { grid = dim3(d.Hq / 4, d.B, cdiv(d.T, 32)); hipLaunchKernelGGL((attn_fwd_k<64, 2, true, true, true>), grid, dim3(256), 0, st, a); }
     else if (gq64 == 4) { grid = dim3(d.Hq / 4, d.B, cdiv(d.T, 16)); hipLaunchKernelGGL((attn_fwd_k<64, 1, true, true, true>), grid, dim3(256), 0, st, a); }
     else
@@ -1359,7 +1358,7 @@ int attention_fwd(hipStream_t st, int dtype, const AttnDesc& d) {
     else if (qt == 3) FWD(64, 3);
     else if (qt == 2) {
       // tuning option 20 = 1: the rounds 1-5 form of the row max (ds_bpermute shuffles) - A/B only, bit-identical
-      if (g_options[20] == 1 && tr) hipLaunchKernelGGL((attn_fwd_k<64, 2, true, false>), grid, dim3(256), 0, st, a);
+      if (opt(UVX_OPT_ATTN_FWD64_BPERMUTE_MAX) == 1 && tr) hipLaunchKernelGGL((attn_fwd_k<64, 2, true, false>), grid, dim3(256), 0, st, a);
       else FWD(64, 2);
     }
     else FWD(64, 1);
@@ -1369,7 +1368,7 @@ int attention_fwd(hipStream_t st, int dtype, const AttnDesc& d) {
     // 160 blocks are 6 % slower and keep the default form).  Tuning option 25: 0 = this rule, 1 / 3 / 4 = force two / three / one query tiles per wave
     // (four spill), 5 = never.  Bit-identical in every form.
     const bool gq_ok = tr && d.causal && d.block == 0 && d.T <= 512 && d.Hkv > 0 && (d.Hq / d.Hkv) % 4 == 0 && d.q_begin == 0;
-    const int gq = !gq_ok || g_options[25] == 5 ? 0 : g_options[25] ? g_options[25] : ((long long)(d.Hq / 4) * d.B * cdiv(d.T, 32) >= 512 ? 1 : 0);
+    const int gq = !gq_ok || opt(UVX_OPT_ATTN_FWD_GQ_FORM) == 5 ? 0 : opt(UVX_OPT_ATTN_FWD_GQ_FORM) ? opt(UVX_OPT_ATTN_FWD_GQ_FORM) : ((long long)(d.Hq / 4) * d.B * cdiv(d.T, 32) >= 512 ? 1 : 0);
     if (gq == 1) { grid = dim3(d.Hq / 4, d.B, cdiv(d.T, 32)); hipLaunchKernelGGL((attn_fwd_k<128, 2, true, true, true>), grid, dim3(256), 0, st, a); }
     else if (gq == 4) { grid = dim3(d.Hq / 4, d.B, cdiv(d.T, 16)); hipLaunchKernelGGL((attn_fwd_k<128, 1, true, true, true>), grid, dim3(256), 0, st, a); }
     else if (gq == 3) { grid = dim3(d.Hq / 4, d.B, cdiv(d.T, 48)); hipLaunchKernelGGL((attn_fwd_k<128, 3, true, true, true>), grid, dim3(256), 0, st, a); }
@@ -1393,7 +1392,7 @@ int lds_tr_probe(hipStream_t st, const int32_t* addr, int32_t* out) {
 // head_dim 128, causal, at most 320 positions (the LLM's training sequences): ONE fused kernel per (batch, query head)
 constexpr int FUSED_TMAX = 320;
 bool attention_bwd_is_fused(int dtype, const AttnDesc& f) {
-  return dtype == DT_BF16 && attention_tr_reads(dtype) && f.D == 128 && f.causal && f.block == 0 && f.T <= FUSED_TMAX && g_options[13] &&
+  return dtype == DT_BF16 && attention_tr_reads(dtype) && f.D == 128 && f.causal && f.block == 0 && f.T <= FUSED_TMAX && opt(UVX_OPT_ATTN_BWD_FUSED) &&
          (f.window <= 0 || f.window >= f.T);   // (a window that covers the sequence is plain causal attention)
 }
 
@@ -1416,7 +1415,7 @@ int attention_bwd(hipStream_t st, int dtype, const AttnBwdDesc& d) {
   a.dkv_part = (d.f.Hq != d.f.Hkv) ? d.dkv_part : nullptr;
   a.o = (bf16_t*)d.f.o;
   a.rope = d.rope_cos_sin;
-  a.tl = (unsigned long long*)g_attn_tl;
+  a.tl = (unsigned long long*)g_tuning.attn_tl;
   // dQ first: it computes delta = rowsum(dO * O) on the fly and leaves it in d.delta for the dK/dV kernel
   const int kv_heads = a.dkv_part ? d.f.Hq : d.f.Hkv;
   // head_dim 128 (the LLM): 128 queries / keys per block (8 waves), 32-row steps, two-deep prefetch.  64-row steps (ST = 64,
@@ -1450,7 +1449,7 @@ int attention_bwd(hipStream_t st, int dtype, const AttnBwdDesc& d) {
     // (bit-identical: each output element still sums its steps in the same order).  Measured (profiles/r06_attn_bwd64_ab.txt, B = 8, 16
     // heads, 1500 frames, pair per layer): one tile each 393.9 us, dQ x2 388.9, both x2 391.0, dK,dV x2 only 399.4, 64-row steps 556,
     // eight-wave blocks 450-469 - a 1 % effect: the pair is latency-, not bandwidth-bound.  Tuning option 19 picks the form (A/B).
-    switch (g_options[19]) {
+    switch (opt(UVX_OPT_ATTN_BWD64_FORM)) {
       case 1: BWD(64, 256, 32, true, 1, 1); break;     // rounds 1-5: one tile per wave
       case 2: BWD(64, 256, 32, true, 2, 2); break;
       case 3: BWD(64, 256, 32, true, 1, 2); break;

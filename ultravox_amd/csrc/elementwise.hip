@@ -7,6 +7,7 @@
 //   transposes / im2col — layout changes feeding the one NT GEMM kernel
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace {
 
@@ -718,7 +719,7 @@ int transpose2d(hipStream_t st, int dtype, const void* in, void* out, int rows, 
 }
 
 int transpose2d_streaming(hipStream_t st, int dtype, const void* in, void* out, int rows, int cols, int ld_in, int ld_out) {
-  return transpose_launch(st, dtype, in, out, rows, cols, ld_in, ld_out, 1, 1, 0, 0, 0, g_options[5] == 0);   // (probe option 5 = 1: plain accesses, for A/B)
+  return transpose_launch(st, dtype, in, out, rows, cols, ld_in, ld_out, 1, 1, 0, 0, 0, opt(UVX_OPT_WT_STREAM_PLAIN_ACCESS) == 0);   // (probe option 5 = 1: plain accesses, for A/B)
 }
 
 int heads_transpose(hipStream_t st, int dtype, const void* in, void* out, int B, int T, int Tp, int H, int D, int ld) {

@@ -24,24 +24,7 @@
 #include <hip/hip_ext.h>
 #include "common.h"
 #include "kernels.h"
-
-namespace uvx {
-int g_gemm_variant = -1; int g_gemm_split = 1;
-// probe hook: per-shape variant overrides (in-situ A/B of the tile choice inside bench.py)
-int g_gemm_ovr_n = 0; int g_gemm_ovr[32][4];
-// probe hook (uvx_set_option): [1] epilogue access: 0 = 8-byte fragment layout, 1 = 16 bytes via v_permlane16_swap
-// (-0.5 ms/step at C2), 2 = row-contiguous through LDS (default), [2] SwiGLU backward fused into the
-// dgrad GEMM (off: measured neutral at C2 - the separate elementwise kernel runs at 6.7 TB/s, the fused epilogue is
-// serialised behind each tile's main loop), [3] loss head on the supervised rows only (on), [4] weight-streaming kernel for
-// M <= 16 (on), [5] residual rows of a wave tile fetched up front in the GEMM epilogue (off: same-box A/B at C2, round 2:
-// 98.2 / 98.6 ms per step with it, 97.5 / 97.6 without - the 2 * MI extra live uint4 per lane cost more than the hidden latency),
-// [6] tile picker uses the merged-phase kernels 31..34 (on; 0 = the round-1 four-phase set 11, 15..19),
-// [7] m-major tile order when the activation matrix is the larger operand (M > N: the encoder's GEMMs; on)
-// [8] (probe builds) let the picker choose the stream-K variants 39..42 (off: measured slower, see the kernel),
-// [10] tail-split threshold in per cent of the whole launch's modelled cost (0 = 88),
-// [9] stream-K flavour: data-parallel rounds before the stream-K part: 1 = all but the last full round ("two-tile"), 0 = none
-int g_options[32] = {0, 2, 0, 1, 1, 0, 1, 1, 0, 1, 0, 1, 1, 1, 1, 0, /*16*/ 1, 1, 0, 0, 0, 0, 0, 0, /*24*/ 0, 0, 0, 0, 0, 0, 0, 0};   // keys: include/uvx.h uvx_set_option
-}  // -1 = automatic; probes may force a tile variant / disable the tail split
+#include "tuning.h"
 
 namespace {
 
@@ -1780,7 +1763,7 @@ int sk_grid() {
 int sk_full_rounds(long long tiles, int grid) {
   if (tiles < grid) return 0;
   const int rounds = (int)(tiles / grid);
-  return uvx::g_options[9] ? rounds - 1 : 0;
+  return uvx::opt(UVX_OPT_STREAMK_TWO_TILE) ? rounds - 1 : 0;
 }
 // time ~ (every block's share of the K-tiles + per-piece fixed costs) x tile area / speed.  A block runs `full` whole
 // tiles plus a share that touches 2 (sometimes 3) tiles: one more pipeline fill than the data-parallel kernel, plus writing /
@@ -1797,9 +1780,9 @@ double sk_cost(int v, int M, int N, int K, int grid) {
 }
 // probes: the tile variant forced for this shape (uvx_gemm_force_variant / uvx_gemm_override_variant), or -1
 int forced_variant(int M, int N, int K) {
-  int forced = uvx::g_gemm_variant;
-  for (int i = 0; i < uvx::g_gemm_ovr_n; ++i)
-    if (uvx::g_gemm_ovr[i][0] == M && uvx::g_gemm_ovr[i][1] == N && uvx::g_gemm_ovr[i][2] == K) forced = uvx::g_gemm_ovr[i][3];
+  int forced = uvx::g_tuning.gemm_variant;
+  for (int i = 0; i < uvx::g_tuning.gemm_ovr_n; ++i)
+    if (uvx::g_tuning.gemm_ovr[i][0] == M && uvx::g_tuning.gemm_ovr[i][1] == N && uvx::g_tuning.gemm_ovr[i][2] == K) forced = uvx::g_tuning.gemm_ovr[i][3];
   return forced;
 }
 int pick_variant(int M, int N, int K, int batch, double* cost_out = nullptr, bool gelu = false) {
@@ -1811,14 +1794,14 @@ int pick_variant(int M, int N, int K, int batch, double* cost_out = nullptr, boo
     return forced;
   }
 #ifdef UVX_PROBES
-  const int skg = batch == 1 && uvx::g_options[8] && uvx::g_options[6] ? sk_grid() : 0;
+  const int skg = batch == 1 && uvx::opt(UVX_OPT_STREAMK_PICK) && uvx::opt(UVX_OPT_MERGED_PHASE_TILES) ? sk_grid() : 0;
 #else
   const int skg = 0;
 #endif
   for (int v = 0; v < kNumVariants; ++v) {
     if (kVariants[v].speed <= 0. || !(is_production(v) || (skg && is_streamk(v)))) continue;
     // option 6 (default 1): merged-phase kernels 31..34 replace their four-phase twins 11, 15..19 (0 = the round-1 set, for A/B)
-    if (v != 0 && ((v >= 31) != (uvx::g_options[6] != 0))) continue;
+    if (v != 0 && ((v >= 31) != (uvx::opt(UVX_OPT_MERGED_PHASE_TILES) != 0))) continue;
     double cost;
     if (is_streamk(v)) {
       // (a launch whose tiles fill whole rounds has nothing to share out; tiny launches stay data-parallel)
@@ -2171,7 +2154,7 @@ SplitPick pick_split(int M, int N, int K, size_t ws_bytes, bool gelu, int force_
   SplitPick best{fv >= 0 ? fv : 0, 1, 1e30};
   for (int v : {0, 34, 33, 32, 31, 59, 60, 18, 19, 11, 15, 16, 17}) {
     if (fv >= 0 ? v != fv : (v > 34 || v < 31) && v != 0) continue;      // (outside the two-set merged-phase kernels - incl. the three-set 59 / 60: only when forced)
-    if (fv < 0 && !uvx::g_options[6] && v != 0) continue;                // (option 6 = 0, the round-1 four-phase set: A/B builds, never split)
+    if (fv < 0 && !uvx::opt(UVX_OPT_MERGED_PHASE_TILES) && v != 0) continue;                // (option 6 = 0, the round-1 four-phase set: A/B builds, never split)
     const long long tiles = (long long)cdiv(M, kVariants[v].bm) * cdiv(N, kVariants[v].bn);
     for (int s = 1; s <= kSplitMax; ++s) {
       if (force_s > 0 && s != force_s) continue;
@@ -2247,7 +2230,7 @@ int uvx::gemm_nt(hipStream_t st, const GemmDesc& d) {
       ((uintptr_t)d.C & 15) == 0 && ((uintptr_t)d.splitk_ws & 15) == 0 && (!d.bias || ((uintptr_t)d.bias & 15) == 0) &&
       (!d.residual || (d.ldr % 8 == 0 && ((uintptr_t)d.residual & 15) == 0)) &&
       (!d.swiglu || (d.ldc2 % 8 == 0 && ((uintptr_t)d.C2 & 15) == 0));      // (the reduce kernel's 16-byte accesses apply)
-  if (uvx::g_gemm_variant < 0 && uvx::gemm_skinny_applicable(d)) {
+  if (uvx::g_tuning.gemm_variant < 0 && uvx::gemm_skinny_applicable(d)) {
     // (M = 17..64 with scratch: the tiled split-K path only where the picker really splits - K/64 < 8, too little scratch or option 6 = 0
     //  leave s = 1, and an UNSPLIT 128 x 128 / 128 x 256 tile on a handful of CUs is slower than the staged skinny kernel: ADVICE r5)
     const bool tiled = split_ok && d.M > 16 && pick_split(d.M, d.N, d.K, d.splitk_ws_bytes, d.act == 1, d.splitk_force).s > 1;
@@ -2262,9 +2245,9 @@ int uvx::gemm_nt(hipStream_t st, const GemmDesc& d) {
   a.sA = d.sA; a.sB = d.sB; a.sC = d.sC; a.sR = d.sR;
   a.act = d.act; a.out_f32 = d.out_f32; a.accumulate = d.accumulate; a.alpha = d.alpha;
   a.C2 = (bf16_t*)d.C2; a.ldc2 = d.ldc2; a.swiglu = d.swiglu;
-  a.wide_io = uvx::g_options[1];
-  a.sw_stage = uvx::g_options[2] != 1;     // SwiGLU-backward epilogue through the LDS stage (option 2 = 1: the round-2 fragment-layout form)
-  a.m_major = uvx::g_options[7] && d.M > d.N && (d.batch <= 1);
+  a.wide_io = uvx::opt(UVX_OPT_EPILOGUE_IO);
+  a.sw_stage = uvx::opt(UVX_OPT_SWIGLU_BWD_IN_DGRAD) != 1;     // SwiGLU-backward epilogue through the LDS stage (option 2 = 1: the round-2 fragment-layout form)
+  a.m_major = uvx::opt(UVX_OPT_M_MAJOR_TILES) && d.M > d.N && (d.batch <= 1);
   a.m_dev = d.m_dev; a.m_dev_off = d.m_dev_off;
   a.sk_full = 0; a.sk_ws = nullptr; a.sk_flags = nullptr; a.sk_epoch = 0; a.ksplit = 1;
   a.b_kn = d.b_kn;
@@ -2306,7 +2289,7 @@ int uvx::gemm_nt(hipStream_t st, const GemmDesc& d) {
       const dim3 rgrid((unsigned)((items + 255) / 256));
       // the RMSNorm that follows this linear, in the same launch (one block per row), where the caller asked for it
       // (N = 512 / 1024 / 2048: rmsnorm_fwd runs its one-wave-per-row kernel there - another summation order, so those widths keep the separate launch)
-      const bool with_norm = d.norm_w && d.norm_out && !d.swiglu && uvx::g_options[17] && d.N <= 256 * 8 * kReduceNormMaxChunks &&
+      const bool with_norm = d.norm_w && d.norm_out && !d.swiglu && uvx::opt(UVX_OPT_SPLITK_REDUCE_NORM) && d.N <= 256 * 8 * kReduceNormMaxChunks &&
                              d.N != 512 && d.N != 1024 && d.N != 2048 &&
                              d.norm_ld % 8 == 0 && ((uintptr_t)d.norm_w & 15) == 0 && ((uintptr_t)d.norm_out & 15) == 0;
       if (with_norm) {
@@ -2347,7 +2330,7 @@ int uvx::gemm_nt(hipStream_t st, const GemmDesc& d) {
   const int tm = cdiv(d.M, V.bm), tn = cdiv(d.N, V.bn);
   const long long tiles = (long long)tm * tn;
   int n_main = d.N, tail_variant = -1;
-  if (batch == 1 && uvx::g_gemm_split && !is_streamk(variant) && tiles > 256 && tiles % 256 != 0) {
+  if (batch == 1 && uvx::g_tuning.gemm_split && !is_streamk(variant) && tiles > 256 && tiles % 256 != 0) {
     const int full_rounds = (int)(tiles / 256);
     const int main_panels = (int)((full_rounds * 256LL) / tm);           // whole weight panels in the full rounds
     const int tail_n = d.N - main_panels * V.bn;
@@ -2357,7 +2340,7 @@ int uvx::gemm_nt(hipStream_t st, const GemmDesc& d) {
       const double cost_split = variant_cost(variant, d.M, main_panels * V.bn, d.K, 1, gelu) + cost_tail;
       // (the second launch costs a round of its own plus a launch gap: only worth it for a clear modelled win)
       // (probe option 10: the threshold in per cent, 0 = the default 88)
-      const double thr = uvx::g_options[10] > 0 ? uvx::g_options[10] / 100.0 : 0.88;
+      const double thr = uvx::opt(UVX_OPT_TAIL_SPLIT_PCT) > 0 ? uvx::opt(UVX_OPT_TAIL_SPLIT_PCT) / 100.0 : 0.88;
       if (cost_split < thr * cost_whole) { n_main = main_panels * V.bn; tail_variant = tv; }
     }
   }

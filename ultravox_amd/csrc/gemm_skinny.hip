@@ -16,6 +16,7 @@
 // bf16 rounding points as store_tile in gemm.hip).
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace {
 
@@ -457,13 +458,13 @@ static int gemv_rows_per_block(const uvx::GemmDesc& d) {
 // Returns UVX_ERR_UNSUPPORTED (no launch, no error text) when the fused kernel does not serve the problem: the caller then runs the two.
 int gemm_skinny_rmsnorm_bf16(hipStream_t st, const GemmDesc& d, const void* norm_w, float eps, int flavor) {
   const bool common = d.M > 0 && d.batch <= 1 && !d.out_f32 && !d.accumulate && !d.m_dev && d.swiglu != 2 && d.act < 2 && !d.b_kn && d.lda % 8 == 0 &&
-                      d.ldb % 8 == 0 && (!d.swiglu || (d.N % 32 == 0 && d.C2)) && norm_w && uvx::g_options[4] == 1;
+                      d.ldb % 8 == 0 && (!d.swiglu || (d.N % 32 == 0 && d.C2)) && norm_w && uvx::opt(UVX_OPT_SKINNY_GEMM) == 1;
   const bool ok = common && d.M <= 2 && d.K % 8 == 0 && d.K <= 16384 && (size_t)d.M * d.K * 2 <= 64 * 1024;
   // 3..16 rows: the staged MFMA kernel normalises its activation fragments in registers - OPT-IN (option 24 = 1): measured 19-32 % SLOWER per token than
   // the two launches (profiles/r06_decode_norm_in_skinny_ab.txt): the kernel lives on loads in flight per wave and the ~70 VALU instructions per fragment
   // lengthen every wave's step
   const bool ok_staged = common && d.M >= 3 && d.M <= 16 && d.K % 2048 == 0 && d.N % 4 == 0 && d.ldc % 4 == 0 && (!d.swiglu || d.ldc2 % 4 == 0) &&
-                         (!d.residual || d.ldr % 4 == 0) && uvx::g_options[24] == 1;
+                         (!d.residual || d.ldr % 4 == 0) && uvx::opt(UVX_OPT_SKINNY_RMSNORM_STAGED) == 1;
   if (!ok && !ok_staged) return UVX_ERR_UNSUPPORTED;
   SkinnyArgs a;
   a.A = (const bf16_t*)d.A; a.B = (const bf16_t*)d.B; a.C = (bf16_t*)d.C; a.bias = (const bf16_t*)d.bias;
@@ -502,9 +503,9 @@ int gemm_skinny_rmsnorm_bf16(hipStream_t st, const GemmDesc& d, const void* norm
     static PerDeviceOnce attr; \
     UVX_SET_ATTR_ONCE(attr, (gemv_rows_bf16_k<1, RR, RBV, true>), 64 * 1024); \
     hipLaunchKernelGGL((gemv_rows_bf16_k<1, RR, RBV, true>), grid, dim3(512), sh, st, a); } while (0)
-  if (mb == 1 && uvx::g_options[26] == 8) { if (rb == 32) UVX_GEMVN_R(8, 32); else if (rb == 16) UVX_GEMVN_R(8, 16); else UVX_GEMVN_R(8, 8); }
-  else if (mb == 1 && uvx::g_options[26] == 0) { if (rb == 32) UVX_GEMVN_R(2, 32); else if (rb == 16) UVX_GEMVN_R(2, 16); else UVX_GEMVN_R(2, 8); }
-  else if (mb == 1 && uvx::g_options[26] == 16) { if (rb == 32) UVX_GEMVN_R(16, 32); else if (rb == 16) UVX_GEMVN_R(16, 16); else UVX_GEMVN_R(8, 8); }
+  if (mb == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 8) { if (rb == 32) UVX_GEMVN_R(8, 32); else if (rb == 16) UVX_GEMVN_R(8, 16); else UVX_GEMVN_R(8, 8); }
+  else if (mb == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 0) { if (rb == 32) UVX_GEMVN_R(2, 32); else if (rb == 16) UVX_GEMVN_R(2, 16); else UVX_GEMVN_R(2, 8); }
+  else if (mb == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 16) { if (rb == 32) UVX_GEMVN_R(16, 32); else if (rb == 16) UVX_GEMVN_R(16, 16); else UVX_GEMVN_R(8, 8); }
   else
   if (rb == 32) { if (mb == 1) UVX_GEMVN(1, 32); else UVX_GEMVN(2, 32); }
   else if (rb == 16) { if (mb == 1) UVX_GEMVN(1, 16); else UVX_GEMVN(2, 16); }
@@ -516,10 +517,10 @@ int gemm_skinny_rmsnorm_bf16(hipStream_t st, const GemmDesc& d, const void* norm
 
 bool gemm_skinny_applicable(const GemmDesc& d) {
   // (M = 17..64: only the staged kernel serves several activation row tiles)
-  const bool rows_ok = d.M <= 16 || (d.M <= 64 && d.K % 2048 == 0 && uvx::g_options[4] != 2);
+  const bool rows_ok = d.M <= 16 || (d.M <= 64 && d.K % 2048 == 0 && uvx::opt(UVX_OPT_SKINNY_GEMM) != 2);
   return d.M > 0 && rows_ok && d.batch <= 1 && !d.out_f32 && !d.accumulate && !d.m_dev && d.swiglu != 2 && d.act < 2 && !d.b_kn &&
          d.K % 32 == 0 && d.lda % 8 == 0 && d.ldb % 8 == 0 && d.N % 4 == 0 && d.ldc % 4 == 0 &&
-         (!d.swiglu || (d.N % 32 == 0 && d.ldc2 % 4 == 0)) && (!d.residual || d.ldr % 4 == 0) && uvx::g_options[4];
+         (!d.swiglu || (d.N % 32 == 0 && d.ldc2 % 4 == 0)) && (!d.residual || d.ldr % 4 == 0) && uvx::opt(UVX_OPT_SKINNY_GEMM);
 }
 
 int gemm_skinny_bf16(hipStream_t st, const GemmDesc& d) {
@@ -537,7 +538,7 @@ int gemm_skinny_bf16(hipStream_t st, const GemmDesc& d) {
   //  registers halve the occupancy: 70B decode, ms per token, row kernel / MFMA mapping: B = 2: 27.0 / 28.8, B = 3: 34.1 / 29.1,
   //  B = 4: 34.4 / 29.3, B = 8: 53 / 31 - profiles/r04_decode_gemv_batch_ab.txt - so the row-streaming kernel serves M <= 2.
   //  With the halving-butterfly lane reduction and one k-step per trip the picture is the same: B = 4: 37.4 / 29.3, B = 8: 89 / 30.6.)
-  if (d.M <= 2 && uvx::g_options[4] != 2 && d.K % 8 == 0 && (!d.swiglu || d.N % 32 == 0)) {
+  if (d.M <= 2 && uvx::opt(UVX_OPT_SKINNY_GEMM) != 2 && d.K % 8 == 0 && (!d.swiglu || d.N % 32 == 0)) {
     const int rb = gemv_rows_per_block(d);
     const dim3 grid((d.N + rb - 1) / rb);
 #define UVX_GEMV(MB, RR) do { if (rb == 32) hipLaunchKernelGGL((gemv_rows_bf16_k<MB, RR, 32>), grid, dim3(512), 0, st, a); \
@@ -546,9 +547,9 @@ int gemm_skinny_bf16(hipStream_t st, const GemmDesc& d) {
     // Weight rows in flight per wave at M = 1 (tuning option 26; profiles/r06_decode_gemv_rows_in_flight_ab.txt, ms per decoded token, 8B / 70B): 16 rows 4.53 / 28.98,
     // 8 rows 3.70 / 24.41, 4 rows (rounds 4-5) 3.27 / 22.79, 2 rows 3.25 / 22.65 - the default since round 6; 0 = 2 rows, 4 / 8 / 16 force (the lane butterfly
     // folds R values at once, so the forms agree to rounding, not bitwise)
-    if (d.M == 1 && uvx::g_options[26] == 8) UVX_GEMV(1, 8);
-    else if (d.M == 1 && uvx::g_options[26] == 0) UVX_GEMV(1, 2);
-    else if (d.M == 1 && uvx::g_options[26] == 16) { if (rb == 32) hipLaunchKernelGGL((gemv_rows_bf16_k<1, 16, 32>), grid, dim3(512), 0, st, a);
+    if (d.M == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 8) UVX_GEMV(1, 8);
+    else if (d.M == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 0) UVX_GEMV(1, 2);
+    else if (d.M == 1 && uvx::opt(UVX_OPT_GEMV_ROWS_IN_FLIGHT) == 16) { if (rb == 32) hipLaunchKernelGGL((gemv_rows_bf16_k<1, 16, 32>), grid, dim3(512), 0, st, a);
                                                       else if (rb == 16) hipLaunchKernelGGL((gemv_rows_bf16_k<1, 16, 16>), grid, dim3(512), 0, st, a);
                                                       else hipLaunchKernelGGL((gemv_rows_bf16_k<1, 8, 8>), grid, dim3(512), 0, st, a); }
     else if (d.M == 1) UVX_GEMV(1, 4); else UVX_GEMV(2, 4);
@@ -556,7 +557,7 @@ int gemm_skinny_bf16(hipStream_t st, const GemmDesc& d) {
     UVX_LAUNCH_CHECK();
     return UVX_OK;
   }
-  if (d.K % 2048 == 0 && uvx::g_options[4] != 2) {      // weights through a wave-private LDS tile (option 4 = 2: straight fragment loads, A/B)
+  if (d.K % 2048 == 0 && uvx::opt(UVX_OPT_SKINNY_GEMM) != 2) {      // weights through a wave-private LDS tile (option 4 = 2: straight fragment loads, A/B)
     constexpr size_t sh = 8 * 16 * SKS_PITCH;             // 67.6 KB: two blocks per CU
     const bool two = d.swiglu || d.N >= 16384;
     const dim3 grid(two ? (d.N + 31) / 32 : (d.N + 15) / 16);

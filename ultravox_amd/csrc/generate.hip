@@ -501,7 +501,7 @@ int qkv_rope(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, 
 int qkv_rope_append(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, const uvx_llm_layer_t& L, const InferWs& s, const void* n,
                     const int32_t* pos, int B, int Tn, int Tmax, int t0, void* ck, void* cv, int l) {
   const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh, rows = B * Tn;
-  if (dt == DT_BF16 && !c.llm_qk_norm && uvx::g_options[16]) {
+  if (dt == DT_BF16 && !c.llm_qk_norm && uvx::opt(UVX_OPT_PREFILL_ROPE_APPEND_FUSED)) {
     GemmDesc g = lin(n, L.wqkv, s.qkv, rows, s.QKV, c.llm_d);
     g.bias = L.bqkv;
     RC(gemm(st, dt, sk(g, s)));
@@ -731,7 +731,7 @@ extern "C" int32_t uvx_llm_decode(void* stream, const uvx_config_t* cfg, const u
       // the grouped attention kernel rotates q / k and appends the new k / v rows itself (option 23; Gemma-3's local layers have their own table:
       // they keep the separate launch) - otherwise rope_kv_append_k (or, with q / k norms, kv_append_k after qkv_rope) runs first
       const bool grp = sh <= 48 * 1024 && ((dh == 128 && (G == 1 || G == 2 || G == 4 || G == 8)) || (dh == 64 && (G == 1 || G == 2 || G == 4)));
-      const bool in_attn = fuse_rope_append && grp && g_options[23] != 1 && c.llm_flavor != UVX_LLM_GEMMA3;
+      const bool in_attn = fuse_rope_append && grp && opt(UVX_OPT_DECODE_ROPE_APPEND_SEPARATE) != 1 && c.llm_flavor != UVX_LLM_GEMMA3;
       const float* rcs = in_attn ? w->rope_cos_sin : nullptr;
       if (in_attn) {
       } else if (fuse_rope_append) {

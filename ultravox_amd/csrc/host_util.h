@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace uvx {
 
@@ -56,6 +57,6 @@ inline GemmDesc lin(const void* A, const void* W, void* C, int M, int N, int K) 
 // 1 LLM attention backward, 2 LLM attention forward, 4 SwiGLU backward, 8 RMSNorm backward, 16 RMSNorm forward, 32 RoPE forward,
 // 64 attention forward of either audio tower's layer stack, 128 every LayerNorm forward inside that stack (enc_stack.hip: the layers' norms in
 // the forward walks and their recomputes in the backward; not the towers' final LayerNorm)
-inline bool probe_skip(int bit) { return (g_options[15] & bit) != 0; }
+inline bool probe_skip(int bit) { return (opt(UVX_OPT_PROBE_SKIP_MASK) & bit) != 0; }
 
 }  // namespace uvx

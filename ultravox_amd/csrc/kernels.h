@@ -73,13 +73,8 @@ struct GemmDesc {
 size_t gemm_splitk_ws_bytes(int M, int N);   // enough scratch for any split gemm_nt picks on an M x N output
 int gemm_pick_split(int M, int N, int K, size_t ws_bytes, int* variant);   // host only: split factor (1 = none) and tile the model picks
 
-extern int g_gemm_variant;
-extern int g_gemm_split;
-extern int g_options[32];
 int gemm_pick_variant(int M, int N, int K, int batch);  // host only: the tile variant the cost model picks
 int gemm_streamk_timeouts();   // stream-K waits that gave up since the last call (0 = healthy); synchronises
-extern int g_gemm_ovr_n;
-extern int g_gemm_ovr[32][4];
 // bf16 operands, f32 accumulate (MFMA 16x16x32).
 int gemm_nt(hipStream_t st, const GemmDesc& d);
 // gemm_skinny.hip: weight-streaming kernel for M <= 16 rows (the decode step); gemm_nt dispatches to it

@@ -129,7 +129,7 @@ struct Chains {
 };
 Chains make_chains(hipStream_t st, const LlmWs& s, int B, bool allowed) {
   Chains ch;
-  int want = g_options[11] < 2 ? 1 : (g_options[11] > 4 ? 4 : g_options[11]);
+  int want = opt(UVX_OPT_LLM_CHAINS) < 2 ? 1 : (opt(UVX_OPT_LLM_CHAINS) > 4 ? 4 : opt(UVX_OPT_LLM_CHAINS));
   if (want > B) want = B;
   ch.fk = (allowed && want >= 2) ? fork_for_device() : nullptr;
   ch.n = ch.fk ? want : 1;
@@ -207,10 +207,10 @@ struct LlmWalk {
   LlmWalk(const LlmCallDesc& d_, const LlmWs& s_, bool save_)
       : d(d_), c(*d_.cfg), w(d_.w), lora(d_.lora), s(s_), dt(c.dtype), D(c.llm_d), I(c.llm_inter), T(d_.T), Hq(c.llm_heads), Hkv(c.llm_kv_heads),
         dh(c.llm_head_dim), fl(c.llm_flavor), g3(fl == UVX_LLM_GEMMA3), save(save_),
-        top(d_.top_rows || ((d_.rows || d_.compact_in_place) && !d_.lora)), tc(top && g_options[3] && !g3),
-        rope_fused(attention_bwd_fuses_rope(dt) && g_options[14]), wts(c.llm_wt_stream != 0) {
+        top(d_.top_rows || ((d_.rows || d_.compact_in_place) && !d_.lora)), tc(top && opt(UVX_OPT_LOSS_HEAD_SUPERVISED_ROWS) && !g3),
+        rope_fused(attention_bwd_fuses_rope(dt) && opt(UVX_OPT_ATTN_BWD_ROPE_FUSED)), wts(c.llm_wt_stream != 0) {
     const int s16 = d.first_pos / 16 * 16;
-    if (s16 > 0 && s16 < T && (d.top_rows || d.compact_in_place) && !lora && g_options[11] < 2 && g_options[14] &&
+    if (s16 > 0 && s16 < T && (d.top_rows || d.compact_in_place) && !lora && opt(UVX_OPT_LLM_CHAINS) < 2 && opt(UVX_OPT_ATTN_BWD_ROPE_FUSED) &&
         attention_bwd_takes_d_first(dt, causal_gqa_desc(c, s.ls0.qkv, d.B, T, s.Tp, s.QKV, s.OD))) { rs.skip = s16; rs.tc = T - s16; }      // (option 14: RoPE inverted inside the attention backward, by position - rope_k would take the row index)
   }
   int slot_of(int l) const { return save ? l : (l & 1); }
@@ -357,7 +357,7 @@ struct LlmWalk {
       if (d.logits_rows) UVX_HIP(hipMemcpyAsync(d.logits_rows, s.logits, (size_t)d.n_rows * c.vocab * es, hipMemcpyDeviceToDevice, st));
       return UVX_OK;
     }
-    if (d.labels && dt == DT_BF16 && g_options[3]) {
+    if (d.labels && dt == DT_BF16 && opt(UVX_OPT_LOSS_HEAD_SUPERVISED_ROWS)) {
       // Loss path on the SUPERVISED rows only (positions whose next token carries a label): every other row of the
       // logits has zero weight in ForCausalLMLoss and a zero gradient, so the head GEMM, the CE and (uvx_llm_bwd) the
       // head dgrad run on the compacted rows - identical loss and gradients, ~T / n_supervised less head work.  The
@@ -406,7 +406,7 @@ struct LlmWalk {
   int head_bwd(const void* head_t) const {
     const hipStream_t st = d.st;
     const int M = s.M;
-    if (d.compact_in_place || (d.labels && dt == DT_BF16 && g_options[3])) {
+    if (d.compact_in_place || (d.labels && dt == DT_BF16 && opt(UVX_OPT_LOSS_HEAD_SUPERVISED_ROWS))) {
       // compact supervised rows (see head_fwd): d logits in place, head dgrad on those rows, scattered back
       if (!d.compact_in_place)
         RC(ce_loss_fwd_bwd(st, dt, s.logits, d.labels, nullptr, s.ce_scratch, s.logits, d.B, T, c.vocab, c.vocab, d.grad_scale, s.sup));
@@ -487,7 +487,7 @@ struct LlmWalk {
       if (ad_in(l)) RC(mlp_in_adapters_bwd(sx, v, cur, l, L.ln2));
       return rmsnorm_bwd(sx, dt, v.d_n, cur.x_mid, L.ln2, v.dx, v.dx, nullptr, Mv, D, c.rms_eps, fl, nullptr, nullptr, map);
     }
-    if (dt == DT_BF16 && g_options[2] && fl == UVX_LLM_LLAMA && !ad_out(l) && !map.skip) {   // d act = dx . W_down^T with the SwiGLU backward fused into the epilogue: writes d gate|up directly
+    if (dt == DT_BF16 && opt(UVX_OPT_SWIGLU_BWD_IN_DGRAD) && fl == UVX_LLM_LLAMA && !ad_out(l) && !map.skip) {   // d act = dx . W_down^T with the SwiGLU backward fused into the epilogue: writes d gate|up directly
       GemmDesc g = lin_dgrad(v.dx, Lt.wd_t, L.wd, v.d_gu, Mv, I, D);
       g.ldc = 2 * I; g.C2 = cur.gu; g.ldc2 = 2 * I; g.swiglu = 2; g.m_dev = mdev;
       RC(gemm(sx, dt, g));

@@ -7,6 +7,7 @@
 // bf16 rounding points of the GEMM path (which are peft's: lora_A output, lora_B output, the sum).
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 #include "../../include/uvx.h"
 
 namespace {
@@ -353,7 +354,7 @@ int lora_down(hipStream_t st, int dtype, const void* X, long long ldx, const voi
 // q_proj and k_proj together (same M, ldx, ldy, C, r; bf16 register kernel) - else two lora_down calls
 int lora_down2(hipStream_t st, int dtype, const void* X0, const void* X1, long long ldx, const void* W0, const void* W1, void* Y0, void* Y1,
                long long ldy, long long M, int C, int r, float alpha0, float alpha1) {
-  if (M > 0 && dtype == DT_BF16 && r <= 8 && (C == 512 || C == 1024) && M >= 1024 && C % 8 == 0 && ldx % 8 == 0 && g_options[22] != 1) {
+  if (M > 0 && dtype == DT_BF16 && r <= 8 && (C == 512 || C == 1024) && M >= 1024 && C % 8 == 0 && ldx % 8 == 0 && opt(UVX_OPT_LORA_QK_SEPARATE) != 1) {
     const int rpw = 8;
     const dim3 g2((unsigned)((M + 4 * rpw - 1) / (4 * rpw)), 2);
     LoraDown2 q = {{(const bf16_t*)X0, (const bf16_t*)X1}, {(const bf16_t*)W0, (const bf16_t*)W1}, {(bf16_t*)Y0, (bf16_t*)Y1}, {alpha0, alpha1}};
@@ -370,7 +371,7 @@ int lora_down2(hipStream_t st, int dtype, const void* X0, const void* X1, long l
 int lora_up2(hipStream_t st, int dtype, const void* Y0, const void* Y1, long long ldy, const void* W0, const void* W1, void* Z0, void* Z1,
              long long ldz, long long M, int C0, int C1, int r, float alpha0, float alpha1) {
   const size_t esz_ = dtype == DT_BF16 ? 2 : 4;
-  const bool ok = M > 0 && r <= 8 && C0 % 8 == 0 && C1 % 8 == 0 && ldz % 8 == 0 && ldy % 8 == 0 && g_options[22] != 1 &&
+  const bool ok = M > 0 && r <= 8 && C0 % 8 == 0 && C1 % 8 == 0 && ldz % 8 == 0 && ldy % 8 == 0 && opt(UVX_OPT_LORA_QK_SEPARATE) != 1 &&
                   ((uintptr_t)Y0 % (8 * esz_)) == 0 && ((uintptr_t)Y1 % (8 * esz_)) == 0 && ((uintptr_t)W0 % 16) == 0 && ((uintptr_t)W1 % 16) == 0 &&
                   ((uintptr_t)Z0 % 16) == 0 && ((uintptr_t)Z1 % 16) == 0;
   if (ok && Z0 == Z1 && C0 == C1) {      // the same rows twice: one pass, the two terms in order
@@ -468,7 +469,7 @@ int lora_wgrad_batch(hipStream_t st, int dtype, const LoraWgradItem* items, int 
     b.partial[i] = region; b.out[i] = it.out; b.C[i] = it.C; b.transpose_out[i] = it.transpose_out; b.alpha[i] = it.alpha;
     region += (long long)nchunks * r * it.C;
   }
-  if (g_options[22] != 1) {      // (round 6) the n products' partial sums in ONE launch per 8 ranks: blockIdx.z = product
+  if (opt(UVX_OPT_LORA_QK_SEPARATE) != 1) {      // (round 6) the n products' partial sums in ONE launch per 8 ranks: blockIdx.z = product
     const dim3 grid((cmax + 63) / 64, nchunks, n);
     for (int j0 = 0; j0 < r; j0 += 8) {
       if (dtype == DT_BF16) {

@@ -35,7 +35,7 @@ EncStackDesc enc_desc(const uvx_config_t& c, int B, int F, bool train) {
   D.train = train; D.post_ln = false; D.key_padding = true; D.block = c.enc_block;
   // one or two clips (generate() at B = 1, 2): 1500 / 3000 rows are 48 ... 144 of the 128- / 256-wide tiles on 256 CUs
   D.splitk = !train && c.dtype == DT_BF16 && D.M() > 64 && D.M() <= 3072;
-  D.pair_qk = true; D.fuse_gelu = c.dtype == DT_BF16 && g_options[21] != 1; D.mlp_adapters = true;
+  D.pair_qk = true; D.fuse_gelu = c.dtype == DT_BF16 && opt(UVX_OPT_TOWER_GELU_SEPARATE) != 1; D.mlp_adapters = true;
   return D;
 }
 EncWs enc_carve(Arena& a, const uvx_config_t& c, const EncStackDesc& D, int F) {

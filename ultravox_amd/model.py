@@ -968,10 +968,10 @@ class UltravoxModel:
         t_logits = self._workspace("teacher_logits", nt * V * 2).view(self.dtype)[: nt * V]
         am = None if alt_attention_mask is None else alt_attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         side = None
-        # With several LLM layer chains (uvx_set_option(11, n >= 2)) every uvx_llm_fwd* call forks the device's ONE set of side streams
+        # With several LLM layer chains (uvx_set_option(Option.LLM_CHAINS, n >= 2)) every uvx_llm_fwd* call forks the device's ONE set of side streams
         # and events; two calls issued from two streams would share it (ordering held only because one host thread issues
         # everything, and the chains of the two calls serialised on the same side streams) - the teacher then runs on the caller's stream.
-        if getattr(self, "kl_teacher_side_stream", True) and dev.type == "cuda" and l.uvx_get_option(11) < 2:
+        if getattr(self, "kl_teacher_side_stream", True) and dev.type == "cuda" and l.uvx_get_option(_lib.Option.LLM_CHAINS) < 2:
             if "_kl_side" not in self.__dict__:
                 self._kl_side = torch.cuda.Stream(device=dev)
             side = self._kl_side
@@ -1005,7 +1005,7 @@ class UltravoxModel:
         self._llm_ctx = (B, T, nb, "rows")        # forward_backward: uvx_llm_bwd_rows
         self._llm_train_pair = False
         # (round 6: uvx_llm_fwd_rows / uvx_llm_bwd_rows run the last layer's row-wise half on the listed rows only, like the CE pair)
-        self._llm_top_rows = not self.config.text_config.is_gemma3 and l.uvx_get_option(3) != 0
+        self._llm_top_rows = not self.config.text_config.is_gemma3 and l.uvx_get_option(_lib.Option.LOSS_HEAD_SUPERVISED_ROWS) != 0
         return CausalLMOutputWithPast(loss=loss[0], logits=None)
 
     @torch.no_grad()
@@ -1581,8 +1581,9 @@ class UltravoxTrainer:
 
     # the two schedules worth trying (profiles/r03_*): ONE layer chain with the fused attention backward (fewer, longer kernels;
     # wins by 1-4 ms per step on the faster MI355X boxes) and TWO chains with the dQ + dK/dV kernel pair (the chains fill each
-    # other's GEMM tail rounds; wins by up to 3 ms on the slower ones).  Keys are uvx_set_option keys.
-    SCHEDULES = ({11: 1, 13: 1}, {11: 2, 13: 0})
+    # other's GEMM tail rounds; wins by up to 3 ms on the slower ones).  Keys are uvx_set_option keys (the tuner and the checkpoint keep
+    # them as plain ints).
+    SCHEDULES = ({_lib.Option.LLM_CHAINS: 1, _lib.Option.ATTN_BWD_FUSED: 1}, {_lib.Option.LLM_CHAINS: 2, _lib.Option.ATTN_BWD_FUSED: 0})
 
     def autotune_schedule(self, candidates=None, rounds: int = 2) -> None:
         """Arms the tuner: the next 1 + rounds * len(candidates) calls of train_step (one throw-away step first) alternate
@@ -1593,7 +1594,7 @@ class UltravoxTrainer:
         box.  For reproducible runs / bit-exact resume keep the library default (do not call this) or pass candidates that differ in
         option 11 only (bit-identical); the verdict is saved by `save_checkpoint` and re-applied by `load_checkpoint`.  The options
         are process-global: tuning one trainer sets the schedule of every model in the process."""
-        cands = [dict(c) for c in (candidates or self.SCHEDULES)]
+        cands = [{int(k): v for k, v in c.items()} for c in (candidates or self.SCHEDULES)]
         self._tune = {"cands": cands, "plan": [None] + [i for _ in range(rounds) for i in range(len(cands))], "i": 0, "t": {},
                       "pending": None}
         self.llm_schedule = None
@@ -1614,7 +1615,7 @@ class UltravoxTrainer:
             best = min(tn["t"], key=lambda c: min(tn["t"][c]))
             self._apply_schedule(tn["cands"][best])
             self.llm_schedule = dict(tn["cands"][best])
-            self.schedule_chains = int(self.llm_schedule.get(11, 0)) or None
+            self.schedule_chains = int(self.llm_schedule.get(_lib.Option.LLM_CHAINS, 0)) or None
             self.schedule_timings = {json.dumps(tn["cands"][c], sort_keys=True): min(v) for c, v in tn["t"].items()}
             self._tune = None
             return
