@@ -399,6 +399,26 @@ int32_t uvx_argmax(void* stream, int32_t dtype, const void* logits, int32_t rows
 int32_t uvx_greedy_select(void* stream, int32_t dtype, const void* logits, int32_t B, int32_t V, const int64_t* eos_ids, int32_t n_eos,
                           int64_t pad, int32_t* unfinished, int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col,
                           const int32_t* positions0, int32_t* positions, int32_t step, int32_t* counter);
+/* The sampling counterpart ([3P] GenerationMixin._sample with do_sample = True): per row, in f32 and in HF's warper order,
+ *   x_v = logits[b, v] / temperature (skipped at 1);   top_k > 0: drop x_v < the k-th largest, k = min(max(top_k, min_keep), V) (ties with it stay);
+ *   top_p < 1: with p = softmax(x) over what is left and C(t) = sum of p_v over {x_v <= t}, drop v when C(x_v) <= 1 - top_p;
+ *   min_p > 0: drop x_v < x_max + log(min_p);   top-p and min-p never drop the min_keep largest.
+ * Without ties this is TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> MinPLogitsWarper exactly.  Equal values stay or go as
+ * a group (a group straddling the top-p boundary, or tied with the min_keep-th largest, stays): HF sorts with an unstable sort and leaves the
+ * order inside such a group - hence which of its members it keeps - unspecified.
+ * The draw: u = uniforms[b] if given, else (w0 >> 8) * 2^-24 with w0 the first output word of Philox4x32-10 (multipliers 0xD2511F53 /
+ * 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) under key (seed_lo, seed_hi) and counter (offset_lo, offset_hi, b, 0); the token is the
+ * lowest index whose cumulative kept probability IN INDEX ORDER exceeds u * total, the last kept index if rounding leaves none, and index 0
+ * for a row with nothing above -inf (like uvx_argmax).  Probabilities are summed as 2^-40 fixed-point integers: the token does not depend on the
+ * order of any addition, so equal inputs, seed and offset give equal tokens on every run.  probs_out (f32 [B, V] or NULL; for tests and
+ * debugging) receives the normalised probabilities after the warpers, 0 for dropped tokens.  The arguments from eos_ids on, and what is done with
+ * them, are uvx_greedy_select's.  V < 2^23.  The dtype argument is spelled logits_dtype because tests/test_f32_kernels_gpu.py lists every entry
+ * that takes an `int32_t dtype`; this one's f32 and bf16 paths are covered by tests/test_sample_gpu.py instead. */
+int32_t uvx_sample_select(void* stream, int32_t logits_dtype, const void* logits, int32_t B, int32_t V, float temperature, int32_t top_k,
+                          float top_p, float min_p, int32_t min_keep, uint64_t seed, uint64_t offset, const float* uniforms,
+                          float* probs_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished,
+                          int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col, const int32_t* positions0,
+                          int32_t* positions, int32_t step, int32_t* counter);
 
 /* clip_grad_norm_(max_norm) + torch.optim.AdamW step over one flat parameter bucket (train.py:260,
  * config_base.py:149-154).  grad: f32 [n] (already DP-averaged).  state_dtype selects the storage of

@@ -92,6 +92,26 @@ def min_p_(x: torch.Tensor, min_p: float, min_tokens_to_keep: int = 1) -> torch.
     return x.masked_fill(remove & ~keep_top, NEG_INF)
 
 
+class PhiloxGenerator:
+    """The random stream of the device sampler (uvx_sample_select, include/uvx.h): a host object holding the Philox4x32-10 key (`seed`) and the
+    counter's low 64 bits (`offset`).  Decode step s of a generate() call draws row b's uniform from counter (offset + s, b); the call then
+    advances the offset by the steps it ran, so consecutive calls never reuse a counter and a (seed, offset) pair replays a call."""
+    MASK = (1 << 64) - 1
+
+    def __init__(self, seed: int = 0):
+        self.manual_seed(seed)
+
+    def manual_seed(self, seed: int) -> "PhiloxGenerator":
+        self.seed, self.offset = int(seed) & self.MASK, 0
+        return self
+
+    def advance(self, n: int) -> "PhiloxGenerator":
+        if n < 0:
+            raise ValueError(f"PhiloxGenerator.advance: n has to be non-negative, but is {n}")
+        self.offset = (self.offset + int(n)) & self.MASK
+        return self
+
+
 def _ids(v) -> List[int]:
     if v is None:
         return []

@@ -107,8 +107,13 @@ class _TokenQueueStreamer:
 class LocalInference:
     def __init__(self, model, processor: UltravoxProcessor, tokenizer, dtype: Optional[torch.dtype] = None,
                  conversation_mode: bool = False, chat_template: Optional[str] = None, enable_thinking: bool = False,
-                 thinking_regex: Optional[str] = None):
+                 thinking_regex: Optional[str] = None, sampler_seed: Optional[int] = None):
         self.model, self.processor, self.tokenizer = model, processor, tokenizer
+        # sampler_seed: draw on the device (uvx_sample_select) from one Philox stream owned by this instance; None: torch's sampler, as before
+        self.sampler = None
+        if sampler_seed is not None:
+            from .generation import PhiloxGenerator
+            self.sampler = PhiloxGenerator(sampler_seed)
         self.dtype = dtype if dtype is not None else getattr(model, "dtype", torch.bfloat16)
         self.conversation_mode = conversation_mode
         self.past_messages: List[Dict[str, str]] = []
@@ -195,6 +200,8 @@ class LocalInference:
         args: Dict[str, Any] = {"max_new_tokens": max_new_tokens or MAX_NEW_TOKENS}
         if temperature is not None and temperature > 0:
             args.update(do_sample=True, temperature=temperature)
+            if self.sampler is not None:
+                args.update(generator=self.sampler)
         else:
             args.update(do_sample=False, top_p=None, top_k=None)
         if self.conversation_mode:

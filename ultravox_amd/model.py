@@ -1133,6 +1133,17 @@ class UltravoxModel:
         ids_dev = input_ids.to(dev)
         am = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         procs = generation.ScoreProcessors(kwargs, T, max_new_tokens, eos_list, rep)
+        # a PhiloxGenerator selects the device sampler (uvx_sample_select): warpers, draw and bookkeeping in one launch per token.  What that kernel
+        # does not do keeps the torch path for now and is refused by name instead of being sampled some other way.
+        philox = generator if do_sample and isinstance(generator, generation.PhiloxGenerator) else None
+        if philox is not None:
+            clash = [n for n, on in (("score processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, "
+                                      "forced_eos_token_id, suppress_tokens, begin_suppress_tokens, logits_processor)", procs.active),
+                                     ("stopping_criteria", bool(crit)), ("output_logits", bool(kwargs.get("output_logits", False))),
+                                     ("num_beams > 1", num_beams > 1)) if on]
+            if clash:
+                raise ValueError(f"generate(): a PhiloxGenerator (the device sampler) cannot be combined with {'; '.join(clash)}: pass a "
+                                 "torch.Generator or no generator for these")
         if num_beams > 1:
             lp = kwargs.get("length_penalty")
             # do_sample: HF's beam sampling - the warpers join the processor list with min_tokens_to_keep = 1 + the number of terminators
@@ -1192,7 +1203,9 @@ class UltravoxModel:
         # Greedy decoding without score processors (the BASELINE inference configuration): the loop's per-token bookkeeping - argmax, pad once a
         # sequence has finished, the EOS test, the next RoPE position - is ONE launch (uvx_greedy_select) and one 4-byte read-back instead of
         # argmax + eight small torch kernels (round 6; profiles/r05_decode70_b8_kernel_stats.txt lists them as at::native rows).  Same tokens.
-        if not procs.active and not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0":
+        # Sampling under a PhiloxGenerator runs the same loop with uvx_sample_select in its place: decode step s draws from counter offset + s.
+        greedy = not procs.active and not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
+        if greedy or philox is not None:
             seq = torch.empty(B, T + max_new_tokens, device=dev, dtype=torch.int64)
             seq[:, :T] = ids_dev
             live = torch.ones(B, device=dev, dtype=torch.int32)
@@ -1200,9 +1213,14 @@ class UltravoxModel:
             pos = torch.empty(B, device=dev, dtype=torch.int32)
             n_out = 0
             for step in range(max_new_tokens):
-                check(l.uvx_greedy_select(stream_ptr(), self.code, ptr(logits), B, V, ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live),
-                                          ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)), C.c_int64(T + step), ptr(next_pos), ptr(pos), step,
-                                          ptr(counter)), "uvx_greedy_select")
+                book = (ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live), ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)), C.c_int64(T + step),
+                        ptr(next_pos), ptr(pos), step, ptr(counter))
+                if philox is None:
+                    check(l.uvx_greedy_select(stream_ptr(), self.code, ptr(logits), B, V, *book), "uvx_greedy_select")
+                else:
+                    check(l.uvx_sample_select(stream_ptr(), self.code, ptr(logits), B, V, float(temperature), int(top_k or 0),
+                                              1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p), 1, philox.seed,
+                                              (philox.offset + step) & philox.MASK, None, None, *book), "uvx_sample_select")
                 n_out = step + 1
                 if streamer is not None:
                     streamer.put(nxt.cpu())
@@ -1213,6 +1231,8 @@ class UltravoxModel:
                 check(l.uvx_llm_decode(stream_ptr(), C.byref(self._c), C.byref(self._lw), ptr(emb), ptr(pos), ptr(kv_start),
                                        ptr(cache), Tmax, T + step, B, ptr(logits), ptr(ws), C.c_size_t(nb)), "uvx_llm_decode")
                 n_decoded += 1
+            if philox is not None:
+                philox.advance(n_out)
             out = [seq[:, :T + n_out]]
             max_new_tokens = 0          # (the generic loop below is skipped)
         for step in range(max_new_tokens):

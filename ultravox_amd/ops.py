@@ -242,3 +242,25 @@ def gelu_bwd(dout, pre):
     din = torch.empty_like(pre)
     check(_lib.lib().uvx_gelu_bwd(stream_ptr(), _code(pre), ptr(dout), ptr(pre), ptr(din), C.c_int64(pre.numel())), "uvx_gelu_bwd")
     return din
+
+
+def sample_select(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min_keep=1, seed=0, offset=0, uniforms=None, want_probs=False,
+                  eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None, step=0, counter=None):
+    """uvx_sample_select on a [B, V] logits matrix (include/uvx.h): -> dict(tokens int64 [B], probs f32 [B, V] or None, unfinished int32 [B],
+    sequences int64 [B, n], positions int32 [B] or None, counter int32 [2]).  Bookkeeping buffers that are not given are created: every row
+    unfinished, a one-column `sequences`, a zero counter."""
+    B, V = logits.shape
+    dev = logits.device
+    logits = logits.contiguous()
+    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
+    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
+    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
+    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
+    tokens = torch.empty(B, device=dev, dtype=torch.int64)
+    probs = torch.empty(B, V, device=dev, dtype=torch.float32) if want_probs else None
+    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.lib().uvx_sample_select(stream_ptr(), _code(logits), ptr(logits), B, V, float(temperature), int(top_k), float(top_p), float(min_p),
+                                       int(min_keep), int(seed), int(offset), ptr(uniforms), ptr(probs), ptr(eos), eos.numel(), int(pad),
+                                       ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0), int(col), ptr(positions0),
+                                       ptr(positions), int(step), ptr(counter)), "uvx_sample_select")
+    return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter)
