@@ -419,6 +419,21 @@ int32_t uvx_sample_select(void* stream, int32_t logits_dtype, const void* logits
                           float* probs_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished,
                           int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col, const int32_t* positions0,
                           int32_t* positions, int32_t step, int32_t* counter);
+/* Greedy decoding under a repetition penalty ([3P] RepetitionPenaltyLogitsProcessor in front of the argmax: what the reference's pipeline runs by
+ * default, ultravox_pipeline.py:100-119).  `seen` is a bitmap, uint32 [B][words] with words >= ceil(V / 32): bit (id & 31) of word (id >> 5) of
+ * row b says that id occurred in row b.  The caller zeroes it; uvx_seen_mark ORs in the bits of ids[b * stride + j], j < n (atomically; ids outside
+ * [0, V) are skipped; n == 0 and B == 0 are no-ops) - once over the whole prompt, padding included, as HF penalises every id of input_ids. */
+int32_t uvx_seen_mark(void* stream, const int64_t* ids, int64_t stride, int32_t B, int32_t n, int32_t V, uint32_t* seen, int32_t words);
+/* uvx_greedy_select on the penalised scores: per element s = (float)logit, and where its bit is set s = s < 0 ? s * penalty : s / penalty (one
+ * correctly rounded f32 operation, as HF writes it); the token is the lowest index of the maximum, NaN never wins, index 0 if nothing is above
+ * -inf.  scores_out (f32 [B, V] or NULL; for tests and debugging) receives every element's penalised score.  The arguments from eos_ids on, and
+ * what is done with them, are uvx_greedy_select's; afterwards the bit of the token WRITTEN (the pad of a finished row included) is set if it lies
+ * in [0, V), so consecutive calls of one loop on one stream see each other's tokens.  penalty > 0 and finite; penalty == 1 selects what
+ * uvx_greedy_select selects.  V < 2^23.  (logits_dtype: as for uvx_sample_select; both paths are covered by tests/test_penalized_select_gpu.py.) */
+int32_t uvx_greedy_select_penalized(void* stream, int32_t logits_dtype, const void* logits, int32_t B, int32_t V, float penalty, uint32_t* seen,
+                                    int32_t words, float* scores_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished,
+                                    int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col, const int32_t* positions0,
+                                    int32_t* positions, int32_t step, int32_t* counter);
 
 /* clip_grad_norm_(max_norm) + torch.optim.AdamW step over one flat parameter bucket (train.py:260,
  * config_base.py:149-154).  grad: f32 [n] (already DP-averaged).  state_dtype selects the storage of

@@ -162,6 +162,12 @@ class ScoreProcessors:
         return bool(self.rep is not None or self.ngram or self.bad_words or self.min_length > 0 or self.min_new > 0 or self.forced_eos or self.suppress
                     or self.begin_suppress or self.user)
 
+    @property
+    def only_repetition_penalty(self) -> bool:
+        """The repetition penalty is the one active processor: what uvx_greedy_select_penalized does on the device."""
+        return bool(self.rep is not None and not (self.ngram or self.bad_words or self.min_length > 0 or self.min_new > 0 or self.forced_eos
+                                                  or self.suppress or self.begin_suppress or self.user))
+
     def __call__(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
         L = ids.shape[1]
         if self.rep is not None:

@@ -127,6 +127,9 @@ class UltravoxModel:
 
     config_class = UltravoxConfig
     accepts_loss_kwargs = False  # ultravox_model.py:50-53: loss = mean over this rank's tokens
+    # generate(): greedy decoding under a repetition penalty alone selects its tokens on the device (uvx_greedy_select_penalized).  __init__ turns it
+    # on; False keeps the host loop (generation.repetition_penalty_ + argmax on f32 scores) - also for an object that never ran __init__
+    penalized_select = False
 
     def __init__(self, config: UltravoxConfig, state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  device: str = "cuda", dtype: Optional[torch.dtype] = None, seed: int = 0,
@@ -151,6 +154,7 @@ class UltravoxModel:
         self.training = False
         # training step: last layer's o_proj / MLP on the supervised rows only (uvx_llm_fwd_train); A/B switch for the probes
         self.top_layer_supervised_rows = os.environ.get("UVX_TOP_LAYER_ROWS", "1") != "0"
+        self.penalized_select = True             # (class attribute above)
         self._llm_train_pair = False             # which uvx_llm_bwd* entry point pairs with the last language_model_forward
         self._llm_top_rows = False
         self._kl_grad_scale = 1.0
@@ -1204,18 +1208,31 @@ class UltravoxModel:
         # sequence has finished, the EOS test, the next RoPE position - is ONE launch (uvx_greedy_select) and one 4-byte read-back instead of
         # argmax + eight small torch kernels (round 6; profiles/r05_decode70_b8_kernel_stats.txt lists them as at::native rows).  Same tokens.
         # Sampling under a PhiloxGenerator runs the same loop with uvx_sample_select in its place: decode step s draws from counter offset + s.
-        greedy = not procs.active and not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
-        if greedy or philox is not None:
+        # Greedy decoding under a repetition penalty and no other processor (the reference pipeline's default call) runs it too, with
+        # uvx_greedy_select_penalized: the ids of the row are a bitmap that uvx_seen_mark fills once from the WHOLE input_ids - left padding, audio
+        # placeholders and a prefix that past_key_values covers included, as HF penalises every id of the row - and the kernel extends per token.
+        device_loop = not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
+        greedy = not procs.active and device_loop
+        penalized = procs.only_repetition_penalty and self.penalized_select and device_loop and rep <= 3.4e38      # (the kernel's penalty is a finite f32)
+        if greedy or penalized or philox is not None:
             seq = torch.empty(B, T + max_new_tokens, device=dev, dtype=torch.int64)
             seq[:, :T] = ids_dev
             live = torch.ones(B, device=dev, dtype=torch.int32)
             counter = torch.zeros(2, device=dev, dtype=torch.int32)
             pos = torch.empty(B, device=dev, dtype=torch.int32)
             n_out = 0
+            if penalized:
+                words = (V + 31) // 32
+                seen = torch.zeros(B, words, device=dev, dtype=torch.int32)
+                ids64 = ids_dev if ids_dev.dtype == torch.int64 and (T == 1 or ids_dev.stride(1) == 1) else ids_dev.to(torch.int64).contiguous()
+                check(l.uvx_seen_mark(stream_ptr(), ptr(ids64), C.c_int64(ids64.stride(0)), B, T, V, ptr(seen), words), "uvx_seen_mark")
             for step in range(max_new_tokens):
                 book = (ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live), ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)), C.c_int64(T + step),
                         ptr(next_pos), ptr(pos), step, ptr(counter))
-                if philox is None:
+                if penalized:
+                    check(l.uvx_greedy_select_penalized(stream_ptr(), self.code, ptr(logits), B, V, float(rep), ptr(seen), words, None, *book),
+                          "uvx_greedy_select_penalized")
+                elif philox is None:
                     check(l.uvx_greedy_select(stream_ptr(), self.code, ptr(logits), B, V, *book), "uvx_greedy_select")
                 else:
                     check(l.uvx_sample_select(stream_ptr(), self.code, ptr(logits), B, V, float(temperature), int(top_k or 0),

@@ -264,3 +264,41 @@ def sample_select(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min
                                        ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0), int(col), ptr(positions0),
                                        ptr(positions), int(step), ptr(counter)), "uvx_sample_select")
     return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter)
+
+
+def seen_words(V: int) -> int:
+    """Words of one row of the `seen` bitmap of uvx_seen_mark / uvx_greedy_select_penalized: ceil(V / 32)."""
+    return (int(V) + 31) // 32
+
+
+def seen_mark(ids, V, seen=None):
+    """uvx_seen_mark (include/uvx.h): ORs the bits of ids int64 [B, n] (unit stride along n, any row stride) into the bitmap `seen`
+    (int32 [B, >= ceil(V / 32)], the kernel's uint32 words; a zeroed one is created if not given) -> seen."""
+    B, n = ids.shape
+    if ids.dtype != torch.int64 or (n > 1 and ids.stride(1) != 1):
+        ids = ids.to(torch.int64).contiguous()
+    if seen is None:
+        seen = torch.zeros(B, seen_words(V), device=ids.device, dtype=torch.int32)
+    check(_lib.lib().uvx_seen_mark(stream_ptr(), ptr(ids), ids.stride(0), B, n, int(V), ptr(seen), seen.shape[1]), "uvx_seen_mark")
+    return seen
+
+
+def greedy_select_penalized(logits, seen, penalty, *, want_scores=False, eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None,
+                            step=0, counter=None):
+    """uvx_greedy_select_penalized on a [B, V] logits matrix and its `seen` bitmap (int32 [B, words], updated in place): -> dict(tokens int64 [B],
+    scores f32 [B, V] or None, unfinished int32 [B], sequences int64 [B, n], positions int32 [B] or None, counter int32 [2], seen).  Bookkeeping
+    buffers that are not given are created as in sample_select."""
+    B, V = logits.shape
+    dev = logits.device
+    logits = logits.contiguous()
+    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
+    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
+    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
+    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
+    tokens = torch.empty(B, device=dev, dtype=torch.int64)
+    scores = torch.empty(B, V, device=dev, dtype=torch.float32) if want_scores else None
+    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.lib().uvx_greedy_select_penalized(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), ptr(seen), seen.shape[1], ptr(scores),
+                                                 ptr(eos), eos.numel(), int(pad), ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0),
+                                                 int(col), ptr(positions0), ptr(positions), int(step), ptr(counter)), "uvx_greedy_select_penalized")
+    return dict(tokens=tokens, scores=scores, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
