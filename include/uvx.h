@@ -434,6 +434,18 @@ int32_t uvx_greedy_select_penalized(void* stream, int32_t logits_dtype, const vo
                                     int32_t words, float* scores_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished,
                                     int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col, const int32_t* positions0,
                                     int32_t* positions, int32_t step, int32_t* counter);
+/* uvx_sample_select on the penalised scores ([3P] RepetitionPenaltyLogitsProcessor in front of the warpers: what the reference's pipeline runs when
+ * it is given a temperature, ultravox_pipeline.py:97-121).  Per element s = (float)logit, and where its bit of `seen` (uvx_seen_mark's bitmap) is set
+ * s = s < 0 ? s * penalty : s / penalty - one correctly rounded f32 operation, as in uvx_greedy_select_penalized; then x = s / temperature (skipped
+ * at 1; HF's order: processors before warpers), and from there every step, argument and output is uvx_sample_select's, probs_out included.
+ * Afterwards the bit of the token WRITTEN (the pad of a finished row included) is set if it lies in [0, V), as uvx_greedy_select_penalized does.
+ * penalty > 0 and finite; penalty == 1, or a bitmap of zeros, gives uvx_sample_select's tokens and probabilities bit for bit.  words >=
+ * ceil(V / 32); V < 2^23.  (logits_dtype: as for uvx_sample_select; both paths are covered by tests/test_sample_penalized_gpu.py.) */
+int32_t uvx_sample_select_penalized(void* stream, int32_t logits_dtype, const void* logits, int32_t B, int32_t V, float penalty, uint32_t* seen,
+                                    int32_t words, float temperature, int32_t top_k, float top_p, float min_p, int32_t min_keep, uint64_t seed,
+                                    uint64_t offset, const float* uniforms, float* probs_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad,
+                                    int32_t* unfinished, int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col,
+                                    const int32_t* positions0, int32_t* positions, int32_t step, int32_t* counter);
 
 /* clip_grad_norm_(max_norm) + torch.optim.AdamW step over one flat parameter bucket (train.py:260,
  * config_base.py:149-154).  grad: f32 [n] (already DP-averaged).  state_dtype selects the storage of

@@ -1,5 +1,5 @@
 // The repetition penalty on a logits row, as a row reader over a "seen" bitmap: what a device-side token selector needs of
-// [3P] RepetitionPenaltyLogitsProcessor.  Used by penalized_select.hip; written so that another selector can read its rows through it.
+// [3P] RepetitionPenaltyLogitsProcessor.  Used by penalized_select.hip (for_row_penalized) and sample_penalized.hip (PenalizedRow).
 //
 // Bitmap: uint32 [B][words], words >= ceil(V / 32); bit (id & 31) of word (id >> 5) of row b = "id occurred in row b" (prompt, padding and
 // generated tokens alike: HF penalises every id of input_ids).  2^23 vocabulary entries are 1 MB per row, so the bitmap is read from global
@@ -14,6 +14,29 @@ namespace uvx {
 __device__ __forceinline__ float penalize(float s, float penalty) { return s < 0.f ? s * penalty : s / penalty; }
 
 __device__ __forceinline__ bool seen_bit(const uint32_t* seen, int id) { return (seen[id >> 5] >> (id & 31)) & 1u; }
+
+// One row behind the penalty, element by element and eight at a time: the reader that the sampler's body (sample.h) is instantiated with.
+// ld8 wants c a multiple of 8 - the eight flags are then one byte of one bitmap word, as in the loop below.
+template <typename T>
+struct PenalizedRow {
+  const T* __restrict__ r;
+  const uint32_t* seen;       // the row's words; the selector sets a bit in them once all its reads are done, so no __restrict__
+  float penalty;
+  __device__ __forceinline__ bool vec(int V) const { return V % 8 == 0 && (reinterpret_cast<uintptr_t>(r) & 15) == 0; }
+  __device__ __forceinline__ void ld8(long long c, float* v) const {
+    ::ld8<T>(r + c, v);
+    const uint32_t flags = (seen[c >> 5] >> (c & 31)) & 0xffu;
+    if (flags) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((flags >> e) & 1u) v[e] = penalize(v[e], penalty);
+    }
+  }
+  __device__ __forceinline__ float ld(long long c) const {
+    const float s = ldf<T>(r + c);
+    return seen_bit(seen, (int)c) ? penalize(s, penalty) : s;
+  }
+};
 
 // f(score_v, v) for every element of the row, score = the penalised f32 logit; 16-byte loads where the row allows them (generate.hip's row_argmax
 // pattern).  In the 8-wide loop c is a multiple of 8: the eight flags are one byte of one bitmap word, and a zero byte skips the penalty work.

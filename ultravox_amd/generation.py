@@ -95,10 +95,13 @@ def min_p_(x: torch.Tensor, min_p: float, min_tokens_to_keep: int = 1) -> torch.
 class PhiloxGenerator:
     """The random stream of the device sampler (uvx_sample_select, include/uvx.h): a host object holding the Philox4x32-10 key (`seed`) and the
     counter's low 64 bits (`offset`).  Decode step s of a generate() call draws row b's uniform from counter (offset + s, b); the call then
-    advances the offset by the steps it ran, so consecutive calls never reuse a counter and a (seed, offset) pair replays a call."""
+    advances the offset by the steps it ran, so consecutive calls never reuse a counter and a (seed, offset) pair replays a call.
+    penalty_on_device=True additionally lets generate() take a `repetition_penalty` that is the only score processor onto the device
+    (uvx_seen_mark + uvx_sample_select_penalized); without the flag that combination is refused, as every other processor is either way."""
     MASK = (1 << 64) - 1
 
-    def __init__(self, seed: int = 0):
+    def __init__(self, seed: int = 0, penalty_on_device: bool = False):
+        self.penalty_on_device = bool(penalty_on_device)
         self.manual_seed(seed)
 
     def manual_seed(self, seed: int) -> "PhiloxGenerator":
@@ -164,7 +167,7 @@ class ScoreProcessors:
 
     @property
     def only_repetition_penalty(self) -> bool:
-        """The repetition penalty is the one active processor: what uvx_greedy_select_penalized does on the device."""
+        """The repetition penalty is the one active processor: what uvx_greedy_select_penalized and uvx_sample_select_penalized do on the device."""
         return bool(self.rep is not None and not (self.ngram or self.bad_words or self.min_length > 0 or self.min_new > 0 or self.forced_eos
                                                   or self.suppress or self.begin_suppress or self.user))
 

@@ -1138,11 +1138,13 @@ class UltravoxModel:
         am = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         procs = generation.ScoreProcessors(kwargs, T, max_new_tokens, eos_list, rep)
         # a PhiloxGenerator selects the device sampler (uvx_sample_select): warpers, draw and bookkeeping in one launch per token.  What that kernel
-        # does not do keeps the torch path for now and is refused by name instead of being sampled some other way.
+        # does not do keeps the torch path for now and is refused by name instead of being sampled some other way.  A generator made with
+        # penalty_on_device=True also takes a repetition penalty that is the only score processor (uvx_sample_select_penalized).
         philox = generator if do_sample and isinstance(generator, generation.PhiloxGenerator) else None
+        sampled_penalized = bool(philox is not None and philox.penalty_on_device and procs.only_repetition_penalty and rep <= 3.4e38)
         if philox is not None:
             clash = [n for n, on in (("score processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, "
-                                      "forced_eos_token_id, suppress_tokens, begin_suppress_tokens, logits_processor)", procs.active),
+                                      "forced_eos_token_id, suppress_tokens, begin_suppress_tokens, logits_processor)", procs.active and not sampled_penalized),
                                      ("stopping_criteria", bool(crit)), ("output_logits", bool(kwargs.get("output_logits", False))),
                                      ("num_beams > 1", num_beams > 1)) if on]
             if clash:
@@ -1211,6 +1213,8 @@ class UltravoxModel:
         # Greedy decoding under a repetition penalty and no other processor (the reference pipeline's default call) runs it too, with
         # uvx_greedy_select_penalized: the ids of the row are a bitmap that uvx_seen_mark fills once from the WHOLE input_ids - left padding, audio
         # placeholders and a prefix that past_key_values covers included, as HF penalises every id of the row - and the kernel extends per token.
+        # Sampling under a PhiloxGenerator(penalty_on_device=True) and a repetition penalty alone (the pipeline's call with a temperature) is the
+        # two together: the same bitmap, uvx_sample_select_penalized per token.
         device_loop = not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
         greedy = not procs.active and device_loop
         penalized = procs.only_repetition_penalty and self.penalized_select and device_loop and rep <= 3.4e38      # (the kernel's penalty is a finite f32)
@@ -1221,7 +1225,7 @@ class UltravoxModel:
             counter = torch.zeros(2, device=dev, dtype=torch.int32)
             pos = torch.empty(B, device=dev, dtype=torch.int32)
             n_out = 0
-            if penalized:
+            if penalized or sampled_penalized:
                 words = (V + 31) // 32
                 seen = torch.zeros(B, words, device=dev, dtype=torch.int32)
                 ids64 = ids_dev if ids_dev.dtype == torch.int64 and (T == 1 or ids_dev.stride(1) == 1) else ids_dev.to(torch.int64).contiguous()
@@ -1234,6 +1238,11 @@ class UltravoxModel:
                           "uvx_greedy_select_penalized")
                 elif philox is None:
                     check(l.uvx_greedy_select(stream_ptr(), self.code, ptr(logits), B, V, *book), "uvx_greedy_select")
+                elif sampled_penalized:
+                    check(l.uvx_sample_select_penalized(stream_ptr(), self.code, ptr(logits), B, V, float(rep), ptr(seen), words, float(temperature),
+                                                        int(top_k or 0), 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p),
+                                                        1, philox.seed, (philox.offset + step) & philox.MASK, None, None, *book),
+                          "uvx_sample_select_penalized")
                 else:
                     check(l.uvx_sample_select(stream_ptr(), self.code, ptr(logits), B, V, float(temperature), int(top_k or 0),
                                               1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p), 1, philox.seed,

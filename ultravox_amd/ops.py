@@ -302,3 +302,28 @@ def greedy_select_penalized(logits, seen, penalty, *, want_scores=False, eos_ids
                                                  ptr(eos), eos.numel(), int(pad), ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0),
                                                  int(col), ptr(positions0), ptr(positions), int(step), ptr(counter)), "uvx_greedy_select_penalized")
     return dict(tokens=tokens, scores=scores, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
+
+
+def sample_select_penalized(logits, seen, penalty, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min_keep=1, seed=0, offset=0, uniforms=None,
+                            want_probs=False, eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None, step=0, counter=None):
+    """uvx_sample_select_penalized on a [B, V] logits matrix and its `seen` bitmap (int32 [B, words], updated in place): sample_select's keywords
+    and its dict, plus `seen`."""
+    B, V = logits.shape
+    if seen.dtype != torch.int32 or seen.dim() != 2 or seen.shape[0] != B or not seen.is_contiguous():      # (the kernel strides the rows by shape[1])
+        raise ValueError(f"sample_select_penalized: `seen` has to be a contiguous int32 [B, words] tensor, but is {seen.dtype} {tuple(seen.shape)} "
+                         f"with strides {tuple(seen.stride())}")
+    dev = logits.device
+    logits = logits.contiguous()
+    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
+    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
+    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
+    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
+    tokens = torch.empty(B, device=dev, dtype=torch.int64)
+    probs = torch.empty(B, V, device=dev, dtype=torch.float32) if want_probs else None
+    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.lib().uvx_sample_select_penalized(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), ptr(seen), seen.shape[1],
+                                                 float(temperature), int(top_k), float(top_p), float(min_p), int(min_keep), int(seed), int(offset),
+                                                 ptr(uniforms), ptr(probs), ptr(eos), eos.numel(), int(pad), ptr(unfinished), ptr(tokens),
+                                                 ptr(sequences), sequences.stride(0), int(col), ptr(positions0), ptr(positions), int(step),
+                                                 ptr(counter)), "uvx_sample_select_penalized")
+    return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
