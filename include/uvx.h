@@ -183,6 +183,32 @@ int32_t uvx_logmel(void* stream, const float* pcm, const float* window, const fl
                    const float* mel_fb, float* out, float* scratch, int32_t B, int32_t L, int32_t n_mels,
                    int32_t F_stride);
 
+/* Polyphase resampling of a ragged batch of PCM clips by the rational factor up / down, in one launch: what scipy.signal.resample_poly(x, up,
+ * down) computes (zero-padded ends, zero phase), with the taps given by the caller.  For the model's 16 kHz and an input rate R:
+ * g = gcd(16000, R), up = 16000 / g, down = R / g.
+ *   taps   f32 [2 * half_len + 1] on the device, taps[half_len + t] the weight at lag t in [-half_len, half_len].  scipy's default filter is,
+ *          with m = max(up, down) and half_len = 10 * m,   w[t] = sinc(t / m) / m * kaiser(2 * half_len + 1, beta = 5.0)[t + half_len],
+ *          h[t] = up * w[t] / sum(w)   (= firwin(2 * half_len + 1, 1 / m, window=("kaiser", 5.0)) * up), designed in float64 and rounded once to
+ *          f32 (ultravox_amd.ops.design_resample_taps); any other table of that layout is applied the same way.
+ *   pcm    the samples of all rows in one device buffer, f32 (pcm_format 0) or int16 (pcm_format 1; a sample counts as x * 2^-15, exact in f32,
+ *          converted inside the kernel).  Row b is the n_in[b] elements from element row_offset[b] on; rows need no alignment beyond their
+ *          element's (an int16 row may start at an odd element).  0 <= n_in[b] <= max_n_in; a row that claims more is read as max_n_in samples.
+ *   out    f32, row b at out + b * out_stride.  With n_out[b] = ceil(n_in[b] * up / down), for k < n_out[b]
+ *              out[b][k] = sum over i in [0, n_in[b]) with |k * down - i * up| <= half_len  of  x_b[i] * taps[half_len + k * down - i * up],
+ *          accumulated in f32 in ascending i, one fused multiply-add per term starting from 0; positions [n_out[b], out_width) are written as
+ *          0.0f, so `out` is directly the zero-padded [B, L] batch uvx_logmel reads; elements from out_width to the stride are not touched.
+ *          A row's bits depend on its samples, the taps, up and down only: not on B, the row's place in the batch, out_width or out_stride.
+ * All index arithmetic is 64-bit (k * down and i * up pass 2^31 for a 44.1 kHz clip of five minutes).  Calls are asynchronous on `stream`.
+ * Status: UVX_ERR_INVALID for a null buffer, a pcm_format other than 0 / 1, up, down or half_len < 1, B outside [0, 65535], out_stride < out_width
+ * and out_width < ceil(max_n_in * up / down); UVX_ERR_UNSUPPORTED, with the limit in the message, for up or down above 1024 or half_len above
+ * 10240 (every rate whose reduced ratio to 16 kHz has both terms <= 1024: 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4 and 192 kHz
+ * among them) - such input is refused, not resampled another way.  B == 0 and out_width == 0 are no-ops.  up == down is not special here (the
+ * callers skip the launch).  The format argument is not spelled `dtype` because tests/test_f32_kernels_gpu.py lists every entry that takes an
+ * `int32_t dtype`; both formats are covered by tests/test_resample_gpu.py. */
+int32_t uvx_resample_poly(void* stream, int32_t pcm_format, const void* pcm, const int64_t* row_offset, const int32_t* n_in, int32_t B,
+                          int32_t max_n_in, int32_t up, int32_t down, const float* taps, int32_t half_len, float* out, int64_t out_stride,
+                          int32_t out_width);
+
 /* ModifiedWhisperEncoder.forward (ultravox_model.py:865-994), inference mode (frozen tower).
  * mel [B, n_mels, F] (f32 if mel_is_f32 else cfg dtype; cast like ultravox_model.py:383);
  * audio_lens [B] int64 mel-frame lengths or NULL (no padding mask); out [B, Te, d], Te = (F-1)/2+1. */

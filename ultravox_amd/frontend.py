@@ -9,7 +9,7 @@ STFT + mel + log runs in libuvx (uvx_logmel) on the GPU.  No CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -69,6 +69,46 @@ def logmel_tables(n_mels: int):
     return window.astype(np.float32), tw_cos, tw_sin, fb
 
 
+def resample_device(clips, sample_rate: int, device, pad_to_multiple_of: Optional[int] = None):
+    """Resamples a list of clips from `sample_rate` to 16 kHz on the GPU (uvx_resample_poly; scipy.signal.resample_poly's definition and default
+    filter).  clips: 1-D numpy arrays or torch tensors, int16 (a sample counts as x / 32768), float32 or float64 (cast to float32 on the host),
+    each its own length.  The PCM is uploaded at its native rate, in one buffer, and nothing comes back.
+    -> (f32 [B, L] on `device`, rows zero-padded beyond their length, L = the longest n_out rounded up to pad_to_multiple_of; the n_out list)"""
+    import torch
+    from . import ops
+
+    sample_rate = int(sample_rate)
+    if sample_rate == 16000:
+        raise ValueError("resample_device: the clips are at 16 kHz already; there is nothing to resample")
+    up, down = ops.resample_ratio(sample_rate)
+    if len(clips) == 0:
+        raise ValueError("resample_device: no clips")
+    rows = []
+    for x in clips:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype not in (torch.int16, torch.float32, torch.float64):
+            raise ValueError("Audio must be float64 or float32 or int16")
+        if t.ndim != 1 or t.numel() == 0:
+            raise ValueError(f"resample_device: a clip has to be 1-D and not empty, but has shape {tuple(t.shape)}")
+        rows.append(t.to(torch.float32) if t.dtype == torch.float64 else t)
+    if len({t.dtype for t in rows}) > 1:      # one format per launch: int16 next to float goes up as float (x / 32768 is exact)
+        rows = [t.to(torch.float32) / 32768.0 if t.dtype == torch.int16 else t for t in rows]
+    lens = [t.numel() for t in rows]
+    if all(not t.is_cuda for t in rows):
+        pcm = torch.cat(rows).to(device)      # one upload
+    else:
+        pcm = torch.cat([t.to(device) for t in rows])
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    row_offset = torch.from_numpy(offsets).to(device)
+    n_in = torch.tensor(lens, dtype=torch.int32).to(device)
+    n_out = [ops.resample_n_out(n, up, down) for n in lens]
+    L = max(n_out)
+    if pad_to_multiple_of:
+        L = -(-L // pad_to_multiple_of) * pad_to_multiple_of
+    out = ops.resample_poly(pcm, row_offset, n_in, up, down, max_n_in=max(lens), out_width=L)
+    return out, n_out
+
+
 class WhisperFeatureExtractor:
     """Device log-mel with the HF feature extractor's call contract (the subset the reference uses)."""
 
@@ -118,6 +158,7 @@ class WhisperFeatureExtractor:
     def __call__(self, raw_speech: Sequence[np.ndarray], sampling_rate: Optional[int] = None,
                  padding: str = "longest", pad_to_multiple_of: Optional[int] = None, truncation: bool = False,
                  return_attention_mask: bool = True, return_tensors: Optional[str] = None, **kwargs):
+        """raw_speech: 1-D clips, numpy arrays or torch tensors; f32 tensors that already lie on the GPU stay there."""
         import torch
 
         if sampling_rate is not None and sampling_rate != self.sampling_rate:
@@ -127,19 +168,34 @@ class WhisperFeatureExtractor:
                 f" was sampled with {self.sampling_rate} and not {sampling_rate}.")
         if padding != "longest" or truncation:
             raise ValueError("only padding='longest', truncation=False (the reference's call) is built")
-        if isinstance(raw_speech, np.ndarray) and raw_speech.ndim == 1:
+        if isinstance(raw_speech, (np.ndarray, torch.Tensor)) and raw_speech.ndim == 1:
             raw_speech = [raw_speech]
-        raw: List[np.ndarray] = [np.asarray(x, dtype=np.float32) for x in raw_speech]
+        on_device = any(isinstance(x, torch.Tensor) and x.is_cuda for x in raw_speech)
+        if on_device:
+            # clips that are already on the GPU (resample_device's output): the padded batch is built there, nothing comes back to the host
+            raw = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, dtype=np.float32)) for x in raw_speech]
+            if any(x.ndim != 1 or (x.is_cuda and x.dtype != torch.float32) for x in raw):
+                raise ValueError("clips on the device have to be 1-D float32 tensors")
+        else:
+            raw = [np.asarray(x, dtype=np.float32) for x in raw_speech]
         lens = [len(x) for x in raw]
         L = max(lens)
         if pad_to_multiple_of:
             L = (L + pad_to_multiple_of - 1) // pad_to_multiple_of * pad_to_multiple_of
-        batch = np.zeros((len(raw), L), np.float32)
         mask = np.zeros((len(raw), L), np.int32)
-        for i, x in enumerate(raw):
-            batch[i, :len(x)] = x
-            mask[i, :len(x)] = 1
-        feats = self.logmel_device(torch.from_numpy(batch).to(self.device))
+        for i, n in enumerate(lens):
+            mask[i, :n] = 1
+        if on_device:
+            dev = next(x.device for x in raw if x.is_cuda)
+            batch = torch.zeros((len(raw), L), device=dev, dtype=torch.float32)
+            for i, x in enumerate(raw):
+                batch[i, :len(x)] = x.to(device=dev, dtype=torch.float32)
+            feats = self.logmel_device(batch)
+        else:
+            batch = np.zeros((len(raw), L), np.float32)
+            for i, x in enumerate(raw):
+                batch[i, :len(x)] = x
+            feats = self.logmel_device(torch.from_numpy(batch).to(self.device))
         # sample mask -> frame mask exactly as the HF extractor rescales it
         fmask = mask[:, ::self.hop_length]
         if L % self.hop_length != 0:

@@ -13,7 +13,10 @@ What differs from the reference, on purpose:
     cached ids part-way (a reply that re-tokenises differently), the rows of the longest common prefix are still reused;
   * `infer_stream` needs one pass, not the reference's two (`:205-223` exist only to snapshot the cache before HF's
     in-place cache grows; a `KVState`'s rows below `cur_len` are never rewritten);
-  * resampling uses scipy's polyphase filter (librosa is not a dependency here).
+  * resampling uses scipy's polyphase filter on the host by default (librosa is not a dependency here); with
+    `resample_on_device=True` the clip goes to the GPU at its native rate and `uvx_resample_poly` applies the same filter
+    there (scipy is then never imported).  The device result differs from scipy's float32 result in the last bits, so it is
+    opt-in.
 """
 import copy
 import dataclasses
@@ -107,8 +110,18 @@ class _TokenQueueStreamer:
 class LocalInference:
     def __init__(self, model, processor: UltravoxProcessor, tokenizer, dtype: Optional[torch.dtype] = None,
                  conversation_mode: bool = False, chat_template: Optional[str] = None, enable_thinking: bool = False,
-                 thinking_regex: Optional[str] = None, sampler_seed: Optional[int] = None):
+                 thinking_regex: Optional[str] = None, sampler_seed: Optional[int] = None, resample_on_device: bool = False):
         self.model, self.processor, self.tokenizer = model, processor, tokenizer
+        # resample_on_device: clips at another rate than 16 kHz are resampled by uvx_resample_poly instead of scipy.  There is no CPU form of it.
+        self.resample_on_device = bool(resample_on_device)
+        if self.resample_on_device:
+            from .frontend import Wav2Vec2FeatureExtractor, WhisperFeatureExtractor
+            if torch.device(getattr(model, "device", "cpu")).type != "cuda":
+                raise ValueError(f"resample_on_device=True needs a model on the GPU, but model.device is {getattr(model, 'device', None)}: "
+                                 "the device resampler has no CPU fallback")
+            if not isinstance(getattr(processor, "audio_processor", None), (WhisperFeatureExtractor, Wav2Vec2FeatureExtractor)):
+                raise ValueError("resample_on_device=True needs this package's audio frontend (frontend.WhisperFeatureExtractor, or "
+                                 f"frontend.Wav2Vec2FeatureExtractor for a raw-waveform tower), not {type(getattr(processor, 'audio_processor', None)).__name__}")
         # sampler_seed: draw on the device (uvx_sample_select) from one Philox stream owned by this instance; None: torch's sampler, as before
         self.sampler = None
         if sampler_seed is not None:
@@ -169,22 +182,35 @@ class LocalInference:
         audio_input = None
         if sample.audio is not None:
             audio = sample.audio
-            if audio.dtype == np.int16:
-                audio = audio / np.float32(32768.0)
-            if audio.dtype not in (np.float64, np.float32):
-                raise ValueError("Audio must be float64 or float32 or int16")
-            if sample.sample_rate != SAMPLE_RATE:
-                from scipy.signal import resample_poly
-                g = math.gcd(SAMPLE_RATE, int(sample.sample_rate))
-                audio = resample_poly(audio, SAMPLE_RATE // g, int(sample.sample_rate) // g, axis=-1).astype(audio.dtype)
-            audio_input = torch.from_numpy(np.ascontiguousarray(audio))
-            if audio_input.ndim == 2:
-                audio_input = audio_input.squeeze(0)
+            if self.resample_on_device and sample.sample_rate != SAMPLE_RATE:
+                audio_input = self._resample_on_device(audio, int(sample.sample_rate))
+            else:
+                if audio.dtype == np.int16:
+                    audio = audio / np.float32(32768.0)
+                if audio.dtype not in (np.float64, np.float32):
+                    raise ValueError("Audio must be float64 or float32 or int16")
+                if sample.sample_rate != SAMPLE_RATE:
+                    from scipy.signal import resample_poly
+                    g = math.gcd(SAMPLE_RATE, int(sample.sample_rate))
+                    audio = resample_poly(audio, SAMPLE_RATE // g, int(sample.sample_rate) // g, axis=-1).astype(audio.dtype)
+                audio_input = torch.from_numpy(np.ascontiguousarray(audio))
+                if audio_input.ndim == 2:
+                    audio_input = audio_input.squeeze(0)
         inputs = self.processor(audio=audio_input, text=text_input, return_tensors="pt", sampling_rate=SAMPLE_RATE)
         inputs = {k: v.to(self.model.device) for k, v in inputs.items()}
         if "audio_values" in inputs:
             inputs["audio_values"] = inputs["audio_values"].to(dtype=self.dtype)
         return inputs
+
+    def _resample_on_device(self, audio, sample_rate: int) -> torch.Tensor:
+        """-> the clip at 16 kHz: a float32 tensor on the GPU for the log-mel frontend; for a raw-waveform tower, whose normalisation is
+        host arithmetic, the resampled clip is copied back once."""
+        from .frontend import WhisperFeatureExtractor, resample_device
+        if getattr(audio, "ndim", 1) == 2 and audio.shape[0] == 1:
+            audio = audio[0]
+        out, n_out = resample_device([audio], sample_rate, self.model.device)
+        clip = out[0, :n_out[0]]
+        return clip if isinstance(self.processor.audio_processor, WhisperFeatureExtractor) else clip.cpu()
 
     def _terminators(self) -> List[int]:
         ids = [self.tokenizer.eos_token_id]

@@ -327,3 +327,80 @@ def sample_select_penalized(logits, seen, penalty, *, temperature=1.0, top_k=0, 
                                                  ptr(sequences), sequences.stride(0), int(col), ptr(positions0), ptr(positions), int(step),
                                                  ptr(counter)), "uvx_sample_select_penalized")
     return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
+
+
+# ---- polyphase resampling (uvx_resample_poly) ----
+RESAMPLE_TILE = 256          # outputs of one row per block: TILE of csrc/resample.h (the tests put n_out on either side of it)
+RESAMPLE_MAX_RATIO = 1024    # up and down are each at most this: MAX_RATIO of csrc/resample.h
+_resample_taps = {}          # (up, down, device) -> (f32 taps on the device, half)
+
+
+def design_resample_taps(up: int, down: int):
+    """The low-pass filter scipy.signal.resample_poly designs by default, in numpy alone: with m = max(up, down) and half = 10 * m,
+    firwin(2 * half + 1, 1 / m, window=("kaiser", 5.0)) * up.  -> (taps float64 [2 * half + 1], half); taps[half + t] is the weight at lag t."""
+    import numpy as np
+
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError(f"design_resample_taps: up={up} and down={down} must be at least 1")
+    m = max(up, down)
+    half = 10 * m
+    t = np.arange(-half, half + 1, dtype=np.float64)
+    w = np.sinc(t / m) / m * np.kaiser(2 * half + 1, 5.0)
+    return up * w / w.sum(), half
+
+
+def resample_ratio(sample_rate: int, target_rate: int = 16000):
+    """-> (up, down) of the reduced fraction target_rate / sample_rate; a ValueError that names the limit if the kernel is not built for it."""
+    import math
+
+    sample_rate = int(sample_rate)
+    if sample_rate < 1:
+        raise ValueError(f"sample rate {sample_rate} must be positive")
+    g = math.gcd(target_rate, sample_rate)
+    up, down = target_rate // g, sample_rate // g
+    if max(up, down) > RESAMPLE_MAX_RATIO:
+        raise ValueError(f"cannot resample {sample_rate} Hz to {target_rate} Hz on the device: the ratio {up}/{down} is beyond the kernel's limit of "
+                         f"{RESAMPLE_MAX_RATIO} for either term (there is no other resampler behind it)")
+    return up, down
+
+
+def resample_taps_device(up: int, down: int, device):
+    """design_resample_taps rounded once to f32, on `device`; cached per (up, down, device).  -> (taps, half)"""
+    key = (int(up), int(down), str(torch.device(device)))
+    if key not in _resample_taps:
+        taps, half = design_resample_taps(up, down)
+        _resample_taps[key] = (torch.from_numpy(taps.astype("float32")).to(device), half)
+    return _resample_taps[key]
+
+
+def resample_n_out(n: int, up: int, down: int) -> int:
+    return -(-int(n) * int(up) // int(down))
+
+
+def resample_poly(pcm, row_offset, n_in, up, down, *, max_n_in, taps=None, half=None, out=None, out_width=None):
+    """uvx_resample_poly (include/uvx.h).  pcm: 1-D int16 or f32 device tensor holding every row; row_offset int64 [B] and n_in int32 [B] on the
+    device; max_n_in: the host's copy of max(n_in).  taps / half default to the cached scipy-default design.  out: f32 [B, >= out_width] with unit
+    stride along a row (created as [B, out_width] if not given); out_width defaults to the n_out of max_n_in.  -> out"""
+    up, down = int(up), int(down)
+    if max(up, down) > RESAMPLE_MAX_RATIO:
+        raise ValueError(f"resample_poly: up={up} down={down} is beyond the kernel's limit of {RESAMPLE_MAX_RATIO} for either term")
+    if pcm.dtype not in (torch.int16, torch.float32) or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError(f"resample_poly: pcm has to be a contiguous 1-D int16 or float32 tensor, but is {pcm.dtype} {tuple(pcm.shape)}")
+    if row_offset.dtype != torch.int64 or n_in.dtype != torch.int32 or row_offset.shape != n_in.shape or n_in.dim() != 1:
+        raise ValueError("resample_poly: row_offset has to be int64 [B] and n_in int32 [B]")
+    B = n_in.shape[0]
+    if B == 0:
+        return torch.empty(0, int(out_width or 0), device=pcm.device, dtype=torch.float32) if out is None else out
+    if taps is None:
+        taps, half = resample_taps_device(up, down, pcm.device)
+    if out_width is None:
+        out_width = resample_n_out(max_n_in, up, down) if out is None else out.shape[1]
+    if out is None:
+        out = torch.empty(B, out_width, device=pcm.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < out_width or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"resample_poly: out has to be f32 [B, >= out_width] with unit stride along a row, but is {out.dtype} {tuple(out.shape)}")
+    check(_lib.lib().uvx_resample_poly(stream_ptr(), 1 if pcm.dtype == torch.int16 else 0, ptr(pcm), ptr(row_offset), ptr(n_in), B, int(max_n_in),
+                                       up, down, ptr(taps), int(half), ptr(out), out.stride(0) if B > 1 else max(out.stride(0), out.shape[1]),
+                                       int(out_width)), "uvx_resample_poly")
+    return out

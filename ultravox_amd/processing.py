@@ -121,7 +121,7 @@ class UltravoxProcessor:
         data: Dict[str, Any] = {}
         is_cont: Sequence[bool] = []
         if len(audios) > 0:
-            audios = [x.numpy() if isinstance(x, torch.Tensor) else x for x in audios]
+            audios = [x.numpy() if isinstance(x, torch.Tensor) and not x.is_cuda else x for x in audios]      # a clip on the GPU stays there
         if len(audios) > 0 and getattr(self.audio_processor.feature_extractor, "hop_length", None) is None:
             # Raw-waveform tower (the `input_values` fallback of :308).  The reference cannot run this branch - it reads
             # feature_extractor.hop_length unconditionally (:284) and chunks [B, mels, F] features - so the contract is the
@@ -143,7 +143,8 @@ class UltravoxProcessor:
         elif len(audios) > 0:
             hop = self.audio_processor.feature_extractor.hop_length
             # at least two hops of samples, the feature extractor's minimum (:283-292)
-            audios = [np.pad(x, (0, 2 * hop - len(x)), mode="constant") if len(x) < 2 * hop else x for x in audios]
+            audios = [x if len(x) >= 2 * hop else F.pad(x, (0, 2 * hop - len(x))) if isinstance(x, torch.Tensor)
+                      else np.pad(x, (0, 2 * hop - len(x)), mode="constant") for x in audios]
             feats = self.audio_processor(audios, sampling_rate=sampling_rate, padding="longest",
                                          pad_to_multiple_of=hop, truncation=False, return_attention_mask=True,
                                          **kwargs)
