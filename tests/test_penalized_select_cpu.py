@@ -256,20 +256,3 @@ def test_score_processors_only_repetition_penalty():
                dict(suppress_tokens=[4]), dict(begin_suppress_tokens=[4]), dict(logits_processor=[lambda i, s: s])):
         assert not mk(1.3, **kw).only_repetition_penalty and mk(1.3, **kw).active, kw
         assert not mk(None, **kw).only_repetition_penalty
-
-
-def test_the_penalised_select_kernels_have_no_scratch_segment():
-    """hipcc's kernel-resource-usage remarks for penalized_select.hip with the package's own flags: the mark kernel and both instantiations of the
-    select kernel, no scratch."""
-    import re
-    import subprocess
-
-    from ultravox_amd import build as B
-    src = B.CSRC / "penalized_select.hip"
-    cmd = [B._hipcc(), *B.FLAGS, *B.EXTRA_FLAGS.get(src.name, []), "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", str(src), "-o", "/dev/null"]
-    err = subprocess.run(cmd, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", err)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)]
-    assert len(names) == len(scratch) == 3, names
-    assert sum("greedy_select_penalized_k" in n for n in names) == 2 and sum("seen_mark_k" in n for n in names) == 1, names
-    assert scratch == [0, 0, 0], list(zip(names, scratch))

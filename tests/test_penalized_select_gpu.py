@@ -1,9 +1,7 @@
-"""uvx_seen_mark and uvx_greedy_select_penalized (include/uvx.h; csrc/penalized_select.hip) on the device against the numpy reference of
+"""uvx_seen_mark and uvx_greedy_select_penalized (include/uvx.h; csrc/select.hip) on the device against the numpy reference of
 tests/penalized_util.py - bitmap, penalised scores and token EXACTLY (no tolerance), the bookkeeping, launch-to-launch visibility - and through
 generate().  f32 and bf16 logits throughout (this file stands in for tests/test_f32_kernels_gpu.py's list of dtype entry points, which the new
 entry point's `logits_dtype` spelling keeps it out of)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -94,7 +92,6 @@ def test_scores_and_token_exactly(V, dtype):
 @pytest.mark.parametrize("V", [4096, 4099])
 def test_crafted_rows(V, dtype):
     """Rows built so that the penalty decides (all values exact in bf16); every one is also held to the reference bitwise by check_select."""
-    from ultravox_amd import _lib as L
     from ultravox_amd import ops
     inf, nan = float("inf"), float("nan")
     g = np.random.default_rng(7)
@@ -141,10 +138,8 @@ def test_crafted_rows(V, dtype):
     a, b = mk(), mk()
     seen = ops.seen_mark(torch.from_numpy(g.integers(0, V, size=(B, 300))).to(DEV), V)
     out = ops.greedy_select_penalized(x, seen, 1.0, eos_ids=eos, pad=pad, col=col, positions0=pos0, step=step, **a)
-    nxt, pos = torch.empty(B, device=DEV, dtype=torch.int64), torch.empty(B, device=DEV, dtype=torch.int32)
-    L.check(L.lib().uvx_greedy_select(L.stream_ptr(), L.dtype_code(dtype), L.ptr(x), B, V, L.ptr(eos), 2, C.c_int64(pad), L.ptr(b["unfinished"]), L.ptr(nxt),
-                                      L.ptr(b["sequences"]), C.c_int64(stride), C.c_int64(col), L.ptr(pos0), L.ptr(pos), step, L.ptr(b["counter"])),
-            "uvx_greedy_select")
+    plain = ops.greedy_select(x, eos_ids=eos, pad=pad, col=col, positions0=pos0, step=step, **b)
+    nxt, pos = plain["tokens"], plain["positions"]
     assert torch.equal(out["tokens"], nxt) and torch.equal(out["positions"], pos)
     for k in ("unfinished", "sequences", "counter"):
         assert torch.equal(a[k], b[k]), k

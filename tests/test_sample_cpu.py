@@ -194,16 +194,19 @@ def test_local_inference_owns_one_philox_stream():
     assert "generator" not in seen[0] and seen[0]["do_sample"]                                        # the default keeps torch's sampler
 
 
-def test_the_sampler_kernels_have_no_scratch_segment():
-    """hipcc's kernel-resource-usage remarks for sample.hip with the package's own flags: both instantiations, no scratch."""
+def test_the_select_kernels_have_no_scratch_segment():
+    """hipcc's kernel-resource-usage remarks for select.hip with the package's own flags: the eight instantiations of the select kernel (reader x
+    chooser x dtype), the mark kernel and both instantiations of the argmax kernel, no scratch."""
     import re
     import subprocess
 
     from ultravox_amd import build as B
-    src = B.CSRC / "sample.hip"
-    cmd = [B._hipcc(), *B.FLAGS, "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", str(src), "-o", "/dev/null"]
+    src = B.CSRC / "select.hip"
+    cmd = [B._hipcc(), *B.FLAGS, *B.EXTRA_FLAGS.get(src.name, []), "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", str(src), "-o", "/dev/null"]
     err = subprocess.run(cmd, capture_output=True, text=True).stderr
     names = re.findall(r"Function Name: (\S+)", err)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)]
-    assert len(names) == len(scratch) == 2 and all("sample_select_k" in n for n in names), names
-    assert scratch == [0, 0], list(zip(names, scratch))
+    assert len(names) == len(scratch) == 11, names
+    count = lambda kernel: sum(kernel in n for n in names)
+    assert (count("select_k"), count("seen_mark_k"), count("argmax_k")) == (8, 1, 2) and len(set(names)) == 11, names
+    assert scratch == [0] * 11, list(zip(names, scratch))

@@ -1,4 +1,4 @@
-"""uvx_sample_select (include/uvx.h; csrc/sample.hip) on the device against the float64 reference of tests/sample_util.py - kept set, probabilities,
+"""uvx_sample_select (include/uvx.h; csrc/select.hip) on the device against the float64 reference of tests/sample_util.py - kept set, probabilities,
 the draw, the Philox stream, the bookkeeping - and through generate() / LocalInference.  f32 and bf16 logits throughout (this file stands in for
 tests/test_f32_kernels_gpu.py's list of dtype entry points, which the new entry point's `logits_dtype` spelling keeps it out of)."""
 import itertools

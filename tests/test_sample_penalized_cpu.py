@@ -380,18 +380,3 @@ def test_pipeline_preprocess_agrees_with_the_recorded_reference(golden_dir):
                 assert np.allclose(g["sampled"], w["sampled"], rtol=0, atol=2e-4), (name, float(np.abs(np.array(g["sampled"]) - w["sampled"]).max()))
             else:
                 assert g == w, (name, k)
-
-
-def test_the_penalised_sampler_kernels_have_no_scratch_segment():
-    """hipcc's kernel-resource-usage remarks for sample_penalized.hip with the package's own flags: both instantiations, no scratch."""
-    import re
-    import subprocess
-
-    from ultravox_amd import build as B
-    src = B.CSRC / "sample_penalized.hip"
-    cmd = [B._hipcc(), *B.FLAGS, *B.EXTRA_FLAGS.get(src.name, []), "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", str(src), "-o", "/dev/null"]
-    err = subprocess.run(cmd, capture_output=True, text=True).stderr
-    names_ = re.findall(r"Function Name: (\S+)", err)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)]
-    assert len(names_) == len(scratch) == 2 and all("sample_select_penalized_k" in n for n in names_), names_
-    assert scratch == [0, 0], list(zip(names_, scratch))

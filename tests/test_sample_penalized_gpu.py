@@ -1,4 +1,4 @@
-"""uvx_sample_select_penalized (include/uvx.h; csrc/sample_penalized.hip) on the device - f32 and bf16 logits throughout - then through generate()
+"""uvx_sample_select_penalized (include/uvx.h; csrc/select.hip) on the device - f32 and bf16 logits throughout - then through generate()
 and UltravoxPipeline.
 
 The reference of a row is a composition of what the suite already trusts: penalized_util.penalized (HF's RepetitionPenaltyLogitsProcessor bit for

@@ -1,5 +1,5 @@
 // The repetition penalty on a logits row, as a row reader over a "seen" bitmap: what a device-side token selector needs of
-// [3P] RepetitionPenaltyLogitsProcessor.  Used by penalized_select.hip (for_row_penalized) and sample_penalized.hip (PenalizedRow).
+// [3P] RepetitionPenaltyLogitsProcessor.  The penalised selectors of select.hip read their rows through PenalizedRow.
 //
 // Bitmap: uint32 [B][words], words >= ceil(V / 32); bit (id & 31) of word (id >> 5) of row b = "id occurred in row b" (prompt, padding and
 // generated tokens alike: HF penalises every id of input_ids).  2^23 vocabulary entries are 1 MB per row, so the bitmap is read from global
@@ -15,8 +15,8 @@ __device__ __forceinline__ float penalize(float s, float penalty) { return s < 0
 
 __device__ __forceinline__ bool seen_bit(const uint32_t* seen, int id) { return (seen[id >> 5] >> (id & 31)) & 1u; }
 
-// One row behind the penalty, element by element and eight at a time: the reader that the sampler's body (sample.h) is instantiated with.
-// ld8 wants c a multiple of 8 - the eight flags are then one byte of one bitmap word, as in the loop below.
+// One row behind the penalty, element by element and eight at a time: a reader for walk_row and the sampler's body (sample.h).
+// ld8 wants c a multiple of 8 - the eight flags are then one byte of one bitmap word, and a zero byte skips the penalty work.
 template <typename T>
 struct PenalizedRow {
   const T* __restrict__ r;
@@ -37,30 +37,5 @@ struct PenalizedRow {
     return seen_bit(seen, (int)c) ? penalize(s, penalty) : s;
   }
 };
-
-// f(score_v, v) for every element of the row, score = the penalised f32 logit; 16-byte loads where the row allows them (generate.hip's row_argmax
-// pattern).  In the 8-wide loop c is a multiple of 8: the eight flags are one byte of one bitmap word, and a zero byte skips the penalty work.
-// Every thread visits its elements in ascending index order.
-template <typename T, typename F>
-__device__ __forceinline__ void for_row_penalized(const T* __restrict__ r, int V, const uint32_t* seen, float penalty, F f) {
-  const int V8 = (V % 8 == 0 && (reinterpret_cast<uintptr_t>(r) & 15) == 0) ? V : 0;
-  for (int c = threadIdx.x * 8; c < V8; c += blockDim.x * 8) {
-    float v[8];
-    ld8<T>(r + c, v);
-    const uint32_t flags = (seen[c >> 5] >> (c & 31)) & 0xffu;
-    if (flags) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if ((flags >> e) & 1u) v[e] = penalize(v[e], penalty);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f(v[e], c + e);
-  }
-  for (int c = V8 + threadIdx.x; c < V; c += blockDim.x) {
-    float s = ldf<T>(r + c);
-    if (seen_bit(seen, c)) s = penalize(s, penalty);
-    f(s, c);
-  }
-}
 
 }  // namespace uvx

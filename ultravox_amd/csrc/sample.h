@@ -1,5 +1,6 @@
-// The body of the device sampler, templated on how a logits row is read: sample.hip reads the row as it lies (uvx_sample_select),
-// sample_penalized.hip reads it through the repetition penalty of penalty.h (uvx_sample_select_penalized).
+// The body of the device sampler, templated on how a logits row is read, and the one walk over a row that every chooser of select.hip uses:
+// select.hip reads the row as it lies (PlainRow below: uvx_sample_select) or through the repetition penalty (PenalizedRow of penalty.h:
+// uvx_sample_select_penalized).
 //
 // Reference: [3P] GenerationMixin._sample with do_sample = True, as the reference's inference path reaches it (LocalInference._generate
 // sets do_sample whenever temperature > 0): TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> MinPLogitsWarper ->
@@ -60,17 +61,24 @@ struct PlainRow {
   __device__ __forceinline__ float ld(long long c) const { return ldf<T>(r + c); }
 };
 
-// f(x_v, v) for every element of the row, 16-byte loads where the row allows them
+// f(score_v, v) for every element of the row as the reader gives it, 16-byte loads where the row allows them (a 128256-wide row took 190 us
+// with 256 threads and 2-byte loads).  Every thread visits its elements in ascending index order.
 template <typename R, typename F>
-__device__ __forceinline__ void for_row(const R& rd, int V, const Row& row, F f) {
+__device__ __forceinline__ void walk_row(const R& rd, int V, F f) {
   const int V8 = rd.vec(V) ? V : 0;
   for (int c = threadIdx.x * 8; c < V8; c += NT * 8) {
     float v[8];
     rd.ld8(c, v);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) f(row.x(v[e]), c + e);
+    for (int e = 0; e < 8; ++e) f(v[e], c + e);
   }
-  for (int c = V8 + threadIdx.x; c < V; c += NT) f(row.x(rd.ld(c)), c);
+  for (int c = V8 + threadIdx.x; c < V; c += NT) f(rd.ld(c), c);
+}
+
+// f(x_v, v): the sampler's view of the same walk
+template <typename R, typename F>
+__device__ __forceinline__ void for_row(const R& rd, int V, const Row& row, F f) {
+  walk_row(rd, V, [&](float score, int c) { f(row.x(score), c); });
 }
 
 __device__ __forceinline__ u64 shfl_up_(u64 v, int o) { return __shfl_up(v, o, 64); }
@@ -282,25 +290,6 @@ __device__ __forceinline__ int sample_row(const R& rd, int V, const SampleArgs& 
     }
   }
   return token;
-}
-
-// The bookkeeping of greedy_select_k (generate.hip), verbatim, by ONE thread of row b's block: -> the token written
-__device__ __forceinline__ int64_t select_bookkeeping(int b, int token, const int64_t* __restrict__ eos_ids, int n_eos, int64_t pad,
-                                                      int32_t* __restrict__ unfinished, int64_t* __restrict__ next_tokens,
-                                                      int64_t* __restrict__ sequences, long long stride, long long col,
-                                                      const int32_t* __restrict__ pos0, int32_t* __restrict__ pos, int step,
-                                                      int32_t* __restrict__ counter) {
-  if (b == 0) counter[(step & 1) ^ 1] = 0;
-  const bool live = unfinished[b] != 0;
-  const int64_t tok = live ? (int64_t)token : pad;
-  next_tokens[b] = tok;
-  sequences[(long long)b * stride + col] = tok;
-  bool still = live;
-  for (int e = 0; e < n_eos; ++e) still = still && tok != eos_ids[e];
-  unfinished[b] = still ? 1 : 0;
-  if (pos) pos[b] = pos0[b] + step;
-  if (still) atomicAdd(&counter[step & 1], 1);
-  return tok;
 }
 
 }  // namespace sampler

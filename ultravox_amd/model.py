@@ -1206,15 +1206,15 @@ class UltravoxModel:
         offs = torch.empty(B + 1, device=dev, dtype=torch.int32)
         unfinished = torch.ones(B, device=dev, dtype=torch.bool)
         n_decoded = 0
-        # Greedy decoding without score processors (the BASELINE inference configuration): the loop's per-token bookkeeping - argmax, pad once a
-        # sequence has finished, the EOS test, the next RoPE position - is ONE launch (uvx_greedy_select) and one 4-byte read-back instead of
-        # argmax + eight small torch kernels (round 6; profiles/r05_decode70_b8_kernel_stats.txt lists them as at::native rows).  Same tokens.
-        # Sampling under a PhiloxGenerator runs the same loop with uvx_sample_select in its place: decode step s draws from counter offset + s.
-        # Greedy decoding under a repetition penalty and no other processor (the reference pipeline's default call) runs it too, with
-        # uvx_greedy_select_penalized: the ids of the row are a bitmap that uvx_seen_mark fills once from the WHOLE input_ids - left padding, audio
+        # The device loop: choosing the token and the loop's per-token bookkeeping - pad once a sequence has finished, the EOS test, the next RoPE
+        # position - are ONE launch and one 4-byte read-back instead of argmax + eight small torch kernels (profiles/r05_decode70_b8_kernel_stats.txt
+        # lists them as at::native rows).  Same tokens.  Its four variants are reader x chooser of csrc/select.hip:
+        #   greedy, no score processor (the BASELINE inference configuration)                        uvx_greedy_select
+        #   greedy under a repetition penalty alone (the reference pipeline's default call)          uvx_greedy_select_penalized
+        #   sampling under a PhiloxGenerator: decode step s draws from counter offset + s            uvx_sample_select
+        #   ... with penalty_on_device=True and a repetition penalty alone                           uvx_sample_select_penalized
+        # The penalised ones read the ids of the row from a bitmap that uvx_seen_mark fills once from the WHOLE input_ids - left padding, audio
         # placeholders and a prefix that past_key_values covers included, as HF penalises every id of the row - and the kernel extends per token.
-        # Sampling under a PhiloxGenerator(penalty_on_device=True) and a repetition penalty alone (the pipeline's call with a temperature) is the
-        # two together: the same bitmap, uvx_sample_select_penalized per token.
         device_loop = not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
         greedy = not procs.active and device_loop
         penalized = procs.only_repetition_penalty and self.penalized_select and device_loop and rep <= 3.4e38      # (the kernel's penalty is a finite f32)
@@ -1225,28 +1225,26 @@ class UltravoxModel:
             counter = torch.zeros(2, device=dev, dtype=torch.int32)
             pos = torch.empty(B, device=dev, dtype=torch.int32)
             n_out = 0
+            # the entry point and its arguments between V and the bookkeeping: how the row is read, then how the token is chosen
+            name = "uvx_sample_select" if philox is not None else "uvx_greedy_select"
+            pen = ()
             if penalized or sampled_penalized:
+                name += "_penalized"
                 words = (V + 31) // 32
                 seen = torch.zeros(B, words, device=dev, dtype=torch.int32)
                 ids64 = ids_dev if ids_dev.dtype == torch.int64 and (T == 1 or ids_dev.stride(1) == 1) else ids_dev.to(torch.int64).contiguous()
                 check(l.uvx_seen_mark(stream_ptr(), ptr(ids64), C.c_int64(ids64.stride(0)), B, T, V, ptr(seen), words), "uvx_seen_mark")
+                pen = (float(rep), ptr(seen), words)
+            if philox is not None:             # (no uniforms, no probs_out)
+                warp = (float(temperature), int(top_k or 0), 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p), 1, philox.seed)
+                head = lambda step: (*pen, *warp, (philox.offset + step) & philox.MASK, None, None)
+            else:                              # (no scores_out)
+                head = lambda step: (*pen, None) if pen else ()
+            book = lambda step: (ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live), ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)),
+                                 C.c_int64(T + step), ptr(next_pos), ptr(pos), step, ptr(counter))
+            select = getattr(l, name)
             for step in range(max_new_tokens):
-                book = (ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live), ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)), C.c_int64(T + step),
-                        ptr(next_pos), ptr(pos), step, ptr(counter))
-                if penalized:
-                    check(l.uvx_greedy_select_penalized(stream_ptr(), self.code, ptr(logits), B, V, float(rep), ptr(seen), words, None, *book),
-                          "uvx_greedy_select_penalized")
-                elif philox is None:
-                    check(l.uvx_greedy_select(stream_ptr(), self.code, ptr(logits), B, V, *book), "uvx_greedy_select")
-                elif sampled_penalized:
-                    check(l.uvx_sample_select_penalized(stream_ptr(), self.code, ptr(logits), B, V, float(rep), ptr(seen), words, float(temperature),
-                                                        int(top_k or 0), 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p),
-                                                        1, philox.seed, (philox.offset + step) & philox.MASK, None, None, *book),
-                          "uvx_sample_select_penalized")
-                else:
-                    check(l.uvx_sample_select(stream_ptr(), self.code, ptr(logits), B, V, float(temperature), int(top_k or 0),
-                                              1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p), 1, philox.seed,
-                                              (philox.offset + step) & philox.MASK, None, None, *book), "uvx_sample_select")
+                check(select(stream_ptr(), self.code, ptr(logits), B, V, *head(step), *book(step)), name)
                 n_out = step + 1
                 if streamer is not None:
                     streamer.put(nxt.cpu())

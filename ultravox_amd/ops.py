@@ -244,26 +244,49 @@ def gelu_bwd(dout, pre):
     return din
 
 
+def _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter):
+    """The bookkeeping buffers of a select entry point, those that are not given created (every row unfinished, a one-column `sequences`, a zero
+    counter): -> (their part of the returned dict, the argument tail from eos_ids to counter)."""
+    B, dev = logits.shape[0], logits.device
+    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
+    out = dict(tokens=torch.empty(B, device=dev, dtype=torch.int64),
+               unfinished=torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished,
+               sequences=torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences,
+               positions=None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32),
+               counter=torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter)
+    # (the 64-bit ones by type: uvx_greedy_select has no argtypes)
+    tail = (ptr(eos), eos.numel(), C.c_int64(int(pad)), ptr(out["unfinished"]), ptr(out["tokens"]), ptr(out["sequences"]),
+            C.c_int64(out["sequences"].stride(0)), C.c_int64(int(col)), ptr(positions0), ptr(out["positions"]), int(step), ptr(out["counter"]))
+    return out, tail
+
+
+def _check_seen(name, seen, B):
+    if seen.dtype != torch.int32 or seen.dim() != 2 or seen.shape[0] != B or not seen.is_contiguous():      # (the kernel strides the rows by shape[1])
+        raise ValueError(f"{name}: `seen` has to be a contiguous int32 [B, words] tensor, but is {seen.dtype} {tuple(seen.shape)} "
+                         f"with strides {tuple(seen.stride())}")
+
+
+def greedy_select(logits, *, eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None, step=0, counter=None):
+    """uvx_greedy_select on a [B, V] logits matrix (include/uvx.h): -> dict(tokens int64 [B], unfinished int32 [B], sequences int64 [B, n],
+    positions int32 [B] or None, counter int32 [2]).  Bookkeeping buffers that are not given are created: every row unfinished, a one-column
+    `sequences`, a zero counter."""
+    B, V = logits.shape
+    logits = logits.contiguous()
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    check(_lib.lib().uvx_greedy_select(stream_ptr(), _code(logits), ptr(logits), B, V, *book), "uvx_greedy_select")
+    return out
+
+
 def sample_select(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min_keep=1, seed=0, offset=0, uniforms=None, want_probs=False,
                   eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None, step=0, counter=None):
-    """uvx_sample_select on a [B, V] logits matrix (include/uvx.h): -> dict(tokens int64 [B], probs f32 [B, V] or None, unfinished int32 [B],
-    sequences int64 [B, n], positions int32 [B] or None, counter int32 [2]).  Bookkeeping buffers that are not given are created: every row
-    unfinished, a one-column `sequences`, a zero counter."""
+    """uvx_sample_select on a [B, V] logits matrix (include/uvx.h): greedy_select's keywords and its dict, plus probs f32 [B, V] or None."""
     B, V = logits.shape
-    dev = logits.device
     logits = logits.contiguous()
-    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
-    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
-    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
-    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
-    tokens = torch.empty(B, device=dev, dtype=torch.int64)
-    probs = torch.empty(B, V, device=dev, dtype=torch.float32) if want_probs else None
-    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    probs = torch.empty(B, V, device=logits.device, dtype=torch.float32) if want_probs else None
     check(_lib.lib().uvx_sample_select(stream_ptr(), _code(logits), ptr(logits), B, V, float(temperature), int(top_k), float(top_p), float(min_p),
-                                       int(min_keep), int(seed), int(offset), ptr(uniforms), ptr(probs), ptr(eos), eos.numel(), int(pad),
-                                       ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0), int(col), ptr(positions0),
-                                       ptr(positions), int(step), ptr(counter)), "uvx_sample_select")
-    return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter)
+                                       int(min_keep), int(seed), int(offset), ptr(uniforms), ptr(probs), *book), "uvx_sample_select")
+    return dict(out, probs=probs)
 
 
 def seen_words(V: int) -> int:
@@ -285,23 +308,16 @@ def seen_mark(ids, V, seen=None):
 
 def greedy_select_penalized(logits, seen, penalty, *, want_scores=False, eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None,
                             step=0, counter=None):
-    """uvx_greedy_select_penalized on a [B, V] logits matrix and its `seen` bitmap (int32 [B, words], updated in place): -> dict(tokens int64 [B],
-    scores f32 [B, V] or None, unfinished int32 [B], sequences int64 [B, n], positions int32 [B] or None, counter int32 [2], seen).  Bookkeeping
-    buffers that are not given are created as in sample_select."""
+    """uvx_greedy_select_penalized on a [B, V] logits matrix and its `seen` bitmap (int32 [B, words], updated in place): greedy_select's keywords
+    and its dict, plus scores f32 [B, V] or None and `seen`."""
     B, V = logits.shape
-    dev = logits.device
+    _check_seen("greedy_select_penalized", seen, B)
     logits = logits.contiguous()
-    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
-    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
-    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
-    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
-    tokens = torch.empty(B, device=dev, dtype=torch.int64)
-    scores = torch.empty(B, V, device=dev, dtype=torch.float32) if want_scores else None
-    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    scores = torch.empty(B, V, device=logits.device, dtype=torch.float32) if want_scores else None
     check(_lib.lib().uvx_greedy_select_penalized(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), ptr(seen), seen.shape[1], ptr(scores),
-                                                 ptr(eos), eos.numel(), int(pad), ptr(unfinished), ptr(tokens), ptr(sequences), sequences.stride(0),
-                                                 int(col), ptr(positions0), ptr(positions), int(step), ptr(counter)), "uvx_greedy_select_penalized")
-    return dict(tokens=tokens, scores=scores, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
+                                                 *book), "uvx_greedy_select_penalized")
+    return dict(out, scores=scores, seen=seen)
 
 
 def sample_select_penalized(logits, seen, penalty, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min_keep=1, seed=0, offset=0, uniforms=None,
@@ -309,24 +325,14 @@ def sample_select_penalized(logits, seen, penalty, *, temperature=1.0, top_k=0, 
     """uvx_sample_select_penalized on a [B, V] logits matrix and its `seen` bitmap (int32 [B, words], updated in place): sample_select's keywords
     and its dict, plus `seen`."""
     B, V = logits.shape
-    if seen.dtype != torch.int32 or seen.dim() != 2 or seen.shape[0] != B or not seen.is_contiguous():      # (the kernel strides the rows by shape[1])
-        raise ValueError(f"sample_select_penalized: `seen` has to be a contiguous int32 [B, words] tensor, but is {seen.dtype} {tuple(seen.shape)} "
-                         f"with strides {tuple(seen.stride())}")
-    dev = logits.device
+    _check_seen("sample_select_penalized", seen, B)
     logits = logits.contiguous()
-    eos = torch.empty(0, device=dev, dtype=torch.int64) if eos_ids is None else eos_ids
-    unfinished = torch.ones(B, device=dev, dtype=torch.int32) if unfinished is None else unfinished
-    sequences = torch.zeros(B, col + 1, device=dev, dtype=torch.int64) if sequences is None else sequences
-    counter = torch.zeros(2, device=dev, dtype=torch.int32) if counter is None else counter
-    tokens = torch.empty(B, device=dev, dtype=torch.int64)
-    probs = torch.empty(B, V, device=dev, dtype=torch.float32) if want_probs else None
-    positions = None if positions0 is None else torch.empty(B, device=dev, dtype=torch.int32)
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    probs = torch.empty(B, V, device=logits.device, dtype=torch.float32) if want_probs else None
     check(_lib.lib().uvx_sample_select_penalized(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), ptr(seen), seen.shape[1],
                                                  float(temperature), int(top_k), float(top_p), float(min_p), int(min_keep), int(seed), int(offset),
-                                                 ptr(uniforms), ptr(probs), ptr(eos), eos.numel(), int(pad), ptr(unfinished), ptr(tokens),
-                                                 ptr(sequences), sequences.stride(0), int(col), ptr(positions0), ptr(positions), int(step),
-                                                 ptr(counter)), "uvx_sample_select_penalized")
-    return dict(tokens=tokens, probs=probs, unfinished=unfinished, sequences=sequences, positions=positions, counter=counter, seen=seen)
+                                                 ptr(uniforms), ptr(probs), *book), "uvx_sample_select_penalized")
+    return dict(out, probs=probs, seen=seen)
 
 
 # ---- polyphase resampling (uvx_resample_poly) ----
