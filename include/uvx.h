@@ -209,6 +209,33 @@ int32_t uvx_resample_poly(void* stream, int32_t pcm_format, const void* pcm, con
                           int32_t max_n_in, int32_t up, int32_t down, const float* taps, int32_t half_len, float* out, int64_t out_stride,
                           int32_t out_width);
 
+/* Zero-mean / unit-variance normalisation of a ragged batch of raw-waveform clips, each over its OWN samples, written as the padded [B, L]
+ * batch a raw-waveform tower (wav2vec2) reads: what the [3P] Wav2Vec2FeatureExtractor computes with do_normalize (zero_mean_unit_var_norm) and
+ * padding="longest".  Two launches on `stream`.
+ *   pcm    the input layout of uvx_resample_poly: all rows in one device buffer, f32 (pcm_format 0) or int16 (pcm_format 1; a sample counts as
+ *          x * 2^-15, exact).  Row b is the n[b] elements from element row_offset[b] on, at any element offset (an int16 row is only 2-byte
+ *          aligned); n[b] is clamped to [0, max_n].  uvx_resample_poly's [B, stride] output is a valid input with row_offset[b] = b * stride.
+ *   out    f32, row b at out + b * out_stride; it must not overlap pcm.  For a row with n = n[b] > 0 and normalize != 0:
+ *              S1 = sum x_i, S2 = sum x_i * x_i (x_i * x_i is exact in float64), both accumulated in float64;
+ *              mean = S1 / n;  var = max(0, S2 / n - mean * mean)  (the population variance);  rstd = 1 / sqrt(var + 1e-7), in float64;
+ *              out[b][i] = (float)(((double)x_i - mean) * rstd)    for i < n.
+ *          With normalize == 0, out[b][i] = (float)x_i: format conversion and padding only (the do_normalize=False extractor).  Positions
+ *          [n[b], out_width) are written as padding_value (its bits); a row with n = 0 is all padding; elements from out_width to the stride
+ *          are not touched.
+ *   order  S1 and S2 are formed over chunks of 16 384 samples counted from the row's own start: within a chunk, 256 strided partial sums
+ *          (partial t holds samples t, t + 256, ... in ascending order) folded by a halving tree (t += t + 128, then + 64, ... + 1); the chunks'
+ *          pairs are then added in ascending chunk order.  No floating-point atomics.  A row's bits depend on its samples and n alone: not on
+ *          B, the row's place in the batch, row_offset, out_width or out_stride.
+ *   workspace  uvx_wave_norm_ws_bytes(B, max_n) = B * ceil(max_n / 16384) * 16 bytes (0 for B <= 0 or max_n <= 0), 16-byte aligned; not
+ *          read or written with normalize == 0, where it may be NULL.
+ * Status: UVX_ERR_INVALID for a null pcm, row_offset, n or out, a pcm_format other than 0 / 1, B outside [0, 65535], max_n < 0,
+ * out_stride < out_width, out_width < max_n, a padding_value that is not finite, and - when normalize != 0 and the size above is not 0 - a null
+ * workspace or ws_bytes below that size.  B == 0 and out_width == 0 are no-ops.  Both formats are covered by tests/test_wavenorm_gpu.py. */
+size_t uvx_wave_norm_ws_bytes(int32_t B, int32_t max_n);
+int32_t uvx_wave_norm(void* stream, int32_t pcm_format, const void* pcm, const int64_t* row_offset, const int32_t* n, int32_t B,
+                      int32_t max_n, int32_t normalize, float padding_value, float* out, int64_t out_stride, int32_t out_width,
+                      void* workspace, size_t ws_bytes);
+
 /* ModifiedWhisperEncoder.forward (ultravox_model.py:865-994), inference mode (frozen tower).
  * mel [B, n_mels, F] (f32 if mel_is_f32 else cfg dtype; cast like ultravox_model.py:383);
  * audio_lens [B] int64 mel-frame lengths or NULL (no padding mask); out [B, Te, d], Te = (F-1)/2+1. */

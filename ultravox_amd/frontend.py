@@ -69,6 +69,35 @@ def logmel_tables(n_mels: int):
     return window.astype(np.float32), tw_cos, tw_sin, fb
 
 
+def _pack_clips(clips, device, what: str):
+    """The input layout of uvx_resample_poly and uvx_wave_norm from a list of clips: 1-D numpy arrays or torch tensors, int16, float32 or
+    float64 (cast to float32 where it lies), each its own length.  Host clips go up in one buffer, int16 as it is.
+    -> (pcm 1-D int16 or f32 on `device`, row_offset int64 [B] and n int32 [B] on `device`, the list of lengths)"""
+    import torch
+
+    if len(clips) == 0:
+        raise ValueError(f"{what}: no clips")
+    rows = []
+    for x in clips:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype not in (torch.int16, torch.float32, torch.float64):
+            raise ValueError("Audio must be float64 or float32 or int16")
+        if t.ndim != 1 or t.numel() == 0:
+            raise ValueError(f"{what}: a clip has to be 1-D and not empty, but has shape {tuple(t.shape)}")
+        rows.append(t.to(torch.float32) if t.dtype == torch.float64 else t)
+    if len({t.dtype for t in rows}) > 1:      # one format per launch: int16 next to float goes up as float (x / 32768 is exact)
+        rows = [t.to(torch.float32) / 32768.0 if t.dtype == torch.int16 else t for t in rows]
+    lens = [t.numel() for t in rows]
+    if all(not t.is_cuda for t in rows):
+        pcm = torch.cat(rows).to(device)      # one upload
+    else:
+        pcm = torch.cat([t.to(device) for t in rows])
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    row_offset = torch.from_numpy(offsets).to(device)
+    n = torch.tensor(lens, dtype=torch.int32).to(device)
+    return pcm, row_offset, n, lens
+
+
 def resample_device(clips, sample_rate: int, device, pad_to_multiple_of: Optional[int] = None):
     """Resamples a list of clips from `sample_rate` to 16 kHz on the GPU (uvx_resample_poly; scipy.signal.resample_poly's definition and default
     filter).  clips: 1-D numpy arrays or torch tensors, int16 (a sample counts as x / 32768), float32 or float64 (cast to float32 on the host),
@@ -81,26 +110,7 @@ def resample_device(clips, sample_rate: int, device, pad_to_multiple_of: Optiona
     if sample_rate == 16000:
         raise ValueError("resample_device: the clips are at 16 kHz already; there is nothing to resample")
     up, down = ops.resample_ratio(sample_rate)
-    if len(clips) == 0:
-        raise ValueError("resample_device: no clips")
-    rows = []
-    for x in clips:
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        if t.dtype not in (torch.int16, torch.float32, torch.float64):
-            raise ValueError("Audio must be float64 or float32 or int16")
-        if t.ndim != 1 or t.numel() == 0:
-            raise ValueError(f"resample_device: a clip has to be 1-D and not empty, but has shape {tuple(t.shape)}")
-        rows.append(t.to(torch.float32) if t.dtype == torch.float64 else t)
-    if len({t.dtype for t in rows}) > 1:      # one format per launch: int16 next to float goes up as float (x / 32768 is exact)
-        rows = [t.to(torch.float32) / 32768.0 if t.dtype == torch.int16 else t for t in rows]
-    lens = [t.numel() for t in rows]
-    if all(not t.is_cuda for t in rows):
-        pcm = torch.cat(rows).to(device)      # one upload
-    else:
-        pcm = torch.cat([t.to(device) for t in rows])
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-    row_offset = torch.from_numpy(offsets).to(device)
-    n_in = torch.tensor(lens, dtype=torch.int32).to(device)
+    pcm, row_offset, n_in, lens = _pack_clips(clips, device, "resample_device")
     n_out = [ops.resample_n_out(n, up, down) for n in lens]
     L = max(n_out)
     if pad_to_multiple_of:
@@ -211,12 +221,26 @@ class Wav2Vec2FeatureExtractor:
     `input_values` [B, L] f32 - what ultravox_processing.py:308 falls back to when there is no `input_features`.
     wav2vec2-large-960h is a feat_extract_norm="group" model: `return_attention_mask` defaults to False there and the model
     runs without a mask; the sample-count mask is still returned on request because the processor needs the lengths.
-    Host arithmetic (a mean and a variance per clip); no device work."""
+    By default this is host arithmetic (numpy: a float32 mean and variance per clip) and `input_values` is a host tensor.  The device
+    path (uvx_wave_norm: float64 sums in a fixed order, one rounding to float32) normalises, pads and leaves `input_values` on the GPU; it
+    is taken when a clip of the call is a CUDA tensor (clips on the GPU stay there, as in WhisperFeatureExtractor) or when the extractor
+    was built with `normalize_on_device=True` (host clips then go up in one buffer, int16 as int16 - a sample counts as x / 32768 -,
+    float64 cast to float32 on the host).  Its result is not bit-equal to numpy's float32 result, so it is opt-in, and there is no CPU form of
+    it.  `attention_mask` is built on the host from the lengths on either path."""
 
     model_input_names = ["input_values", "attention_mask"]
 
-    def __init__(self, sampling_rate: int = 16000, padding_value: float = 0.0, do_normalize: bool = True):
+    def __init__(self, sampling_rate: int = 16000, padding_value: float = 0.0, do_normalize: bool = True, device=None,
+                 normalize_on_device: bool = False):
         self.sampling_rate, self.padding_value, self.do_normalize, self.feature_size = sampling_rate, padding_value, do_normalize, 1
+        self.normalize_on_device = bool(normalize_on_device)
+        self.device = device
+        if self.normalize_on_device:
+            import torch
+            self.device = "cuda" if device is None else device
+            if torch.device(self.device).type != "cuda" or not torch.cuda.is_available():
+                raise ValueError(f"normalize_on_device=True needs a CUDA device, but device is {device!r} and torch.cuda.is_available() is "
+                                 f"{torch.cuda.is_available()}: the device normaliser (uvx_wave_norm) has no CPU form")
 
     @property
     def feature_extractor(self):
@@ -229,7 +253,11 @@ class Wav2Vec2FeatureExtractor:
             raise ValueError(f"The model corresponding to this feature extractor was trained using a sampling rate of "
                              f"{self.sampling_rate}. Please make sure that the provided `raw_speech` input was sampled with "
                              f"{self.sampling_rate} and not {sampling_rate}.")
-        clips = [np.asarray(x, dtype=np.float32).reshape(-1) for x in (raw_speech if isinstance(raw_speech, (list, tuple)) else [raw_speech])]
+        raw = raw_speech if isinstance(raw_speech, (list, tuple)) else [raw_speech]
+        on_device = [x for x in raw if isinstance(x, torch.Tensor) and x.is_cuda]
+        if on_device or self.normalize_on_device:
+            return self._call_device(raw, on_device[0].device if on_device else self.device, pad_to_multiple_of, return_attention_mask)
+        clips = [np.asarray(x, dtype=np.float32).reshape(-1) for x in raw]
         lens = [len(x) for x in clips]
         width = max(lens)
         if pad_to_multiple_of:
@@ -240,6 +268,22 @@ class Wav2Vec2FeatureExtractor:
                 x = (x - x.mean()) / np.sqrt(x.var() + 1e-7)
             out[i, : len(x)] = x
         data = {"input_values": torch.from_numpy(out)}
+        if return_attention_mask:
+            data["attention_mask"] = torch.from_numpy((np.arange(width)[None, :] < np.asarray(lens)[:, None]).astype(np.int32))
+        return data
+
+    def _call_device(self, raw, device, pad_to_multiple_of, return_attention_mask):
+        """One uvx_wave_norm call over all clips; nothing comes back to the host (the mask is built from the lengths)."""
+        import torch
+        from . import ops
+
+        raw = [x.reshape(-1) if isinstance(x, torch.Tensor) else np.asarray(x).reshape(-1) for x in raw]
+        pcm, row_offset, n, lens = _pack_clips(raw, device, "Wav2Vec2FeatureExtractor")
+        width = max(lens)
+        if pad_to_multiple_of:
+            width = -(-width // pad_to_multiple_of) * pad_to_multiple_of
+        data = {"input_values": ops.wave_norm(pcm, row_offset, n, max_n=max(lens), normalize=bool(self.do_normalize),
+                                              padding_value=float(self.padding_value), out_width=width)}
         if return_attention_mask:
             data["attention_mask"] = torch.from_numpy((np.arange(width)[None, :] < np.asarray(lens)[:, None]).astype(np.int32))
         return data

@@ -16,7 +16,8 @@ What differs from the reference, on purpose:
   * resampling uses scipy's polyphase filter on the host by default (librosa is not a dependency here); with
     `resample_on_device=True` the clip goes to the GPU at its native rate and `uvx_resample_poly` applies the same filter
     there (scipy is then never imported).  The device result differs from scipy's float32 result in the last bits, so it is
-    opt-in.
+    opt-in.  For a raw-waveform tower the resampled clip stays on the GPU too: `frontend.Wav2Vec2FeatureExtractor` normalises a
+    clip that lies there with `uvx_wave_norm`; built with `normalize_on_device=True` it also takes a 16 kHz int16 clip as int16.
 """
 import copy
 import dataclasses
@@ -185,9 +186,11 @@ class LocalInference:
             if self.resample_on_device and sample.sample_rate != SAMPLE_RATE:
                 audio_input = self._resample_on_device(audio, int(sample.sample_rate))
             else:
-                if audio.dtype == np.int16:
+                # a 16 kHz int16 clip for a device normaliser goes up as int16 (uvx_wave_norm counts a sample as x / 32768): no host arithmetic
+                int16_as_it_is = audio.dtype == np.int16 and self.resample_on_device and self._normalizes_on_device()
+                if audio.dtype == np.int16 and not int16_as_it_is:
                     audio = audio / np.float32(32768.0)
-                if audio.dtype not in (np.float64, np.float32):
+                if audio.dtype not in (np.float64, np.float32) and not int16_as_it_is:
                     raise ValueError("Audio must be float64 or float32 or int16")
                 if sample.sample_rate != SAMPLE_RATE:
                     from scipy.signal import resample_poly
@@ -203,14 +206,18 @@ class LocalInference:
         return inputs
 
     def _resample_on_device(self, audio, sample_rate: int) -> torch.Tensor:
-        """-> the clip at 16 kHz: a float32 tensor on the GPU for the log-mel frontend; for a raw-waveform tower, whose normalisation is
-        host arithmetic, the resampled clip is copied back once."""
-        from .frontend import WhisperFeatureExtractor, resample_device
+        """-> the clip at 16 kHz, a float32 tensor on the GPU: the log-mel frontend and the raw-waveform extractor (uvx_wave_norm) both keep a
+        clip that lies there on the device."""
+        from .frontend import resample_device
         if getattr(audio, "ndim", 1) == 2 and audio.shape[0] == 1:
             audio = audio[0]
         out, n_out = resample_device([audio], sample_rate, self.model.device)
-        clip = out[0, :n_out[0]]
-        return clip if isinstance(self.processor.audio_processor, WhisperFeatureExtractor) else clip.cpu()
+        return out[0, :n_out[0]]
+
+    def _normalizes_on_device(self) -> bool:
+        from .frontend import Wav2Vec2FeatureExtractor
+        ap = getattr(self.processor, "audio_processor", None)
+        return isinstance(ap, Wav2Vec2FeatureExtractor) and ap.normalize_on_device
 
     def _terminators(self) -> List[int]:
         ids = [self.tokenizer.eos_token_id]

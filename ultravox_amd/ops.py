@@ -410,3 +410,34 @@ def resample_poly(pcm, row_offset, n_in, up, down, *, max_n_in, taps=None, half=
                                        up, down, ptr(taps), int(half), ptr(out), out.stride(0) if B > 1 else max(out.stride(0), out.shape[1]),
                                        int(out_width)), "uvx_resample_poly")
     return out
+
+
+# ---- raw-waveform normalisation (uvx_wave_norm) ----
+WAVENORM_CHUNK = 16384       # samples of one row per partial (S1, S2) pair: CHUNK of csrc/wavenorm.h (the tests put n on either side of it)
+
+
+def wave_norm(pcm, row_offset, n, *, max_n, normalize=True, padding_value=0.0, out=None, out_width=None):
+    """uvx_wave_norm (include/uvx.h).  pcm: 1-D int16 or f32 device tensor holding every row (resample_poly's input layout); row_offset int64
+    [B] and n int32 [B] on the device; max_n: the host's copy of max(n).  normalize=False converts and pads only.  out: f32 [B, >= out_width]
+    with unit stride along a row, not overlapping pcm (created as [B, out_width] if not given); out_width defaults to max_n.  The workspace
+    is allocated here.  -> out"""
+    if pcm.dtype not in (torch.int16, torch.float32) or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError(f"wave_norm: pcm has to be a contiguous 1-D int16 or float32 tensor, but is {pcm.dtype} {tuple(pcm.shape)}")
+    if row_offset.dtype != torch.int64 or n.dtype != torch.int32 or row_offset.shape != n.shape or n.dim() != 1:
+        raise ValueError("wave_norm: row_offset has to be int64 [B] and n int32 [B]")
+    B = n.shape[0]
+    if B == 0:
+        return torch.empty(0, int(out_width or 0), device=pcm.device, dtype=torch.float32) if out is None else out
+    if out_width is None:
+        out_width = int(max_n) if out is None or out.dim() != 2 else out.shape[1]
+    if out is None:
+        out = torch.empty(B, out_width, device=pcm.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < out_width or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"wave_norm: out has to be f32 [B, >= out_width] with unit stride along a row, but is {out.dtype} {tuple(out.shape)}")
+    l = _lib.lib()
+    ws_bytes = int(l.uvx_wave_norm_ws_bytes(B, int(max_n))) if normalize else 0
+    ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8) if ws_bytes else None
+    check(l.uvx_wave_norm(stream_ptr(), 1 if pcm.dtype == torch.int16 else 0, ptr(pcm), ptr(row_offset), ptr(n), B, int(max_n), int(bool(normalize)),
+                          float(padding_value), ptr(out), out.stride(0) if B > 1 else max(out.stride(0), out.shape[1]), int(out_width), ptr(ws),
+                          ws_bytes), "uvx_wave_norm")
+    return out
