@@ -499,6 +499,50 @@ int32_t uvx_sample_select_penalized(void* stream, int32_t logits_dtype, const vo
                                     uint64_t offset, const float* uniforms, float* probs_out, const int64_t* eos_ids, int32_t n_eos, int64_t pad,
                                     int32_t* unfinished, int64_t* next_tokens, int64_t* sequences, int64_t stride, int64_t col,
                                     const int32_t* positions0, int32_t* positions, int32_t step, int32_t* counter);
+/* The token-ban score processors of HF's generate() in the same launch ([3P] NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, ForcedEOSToken,
+ * SuppressTokens, SuppressTokensAtBegin: each sets a set of ids to -inf, the forced step sets the others to 0).  The rules of one generate() call: a
+ * HOST struct of DEVICE pointers (an id list may be NULL only where its count is 0).  Ids are compared by value wherever they stand and are used as a
+ * bit position only inside [0, V). */
+typedef struct {
+  const int64_t* bad_tokens;   /* [n_bad_tokens]: the bad-word entries one after another (lone-EOS entries already dropped, as HF drops them) */
+  const int32_t* bad_offsets;  /* [n_bad + 1]: entry e is bad_tokens[bad_offsets[e] .. bad_offsets[e + 1]); an entry that does not lie inside
+                                * [0, n_bad_tokens] with at least one token is skipped */
+  const int64_t* min_ids;      /* [n_min]: the ids banned while UVX_BAN_MIN is set (the non-negative EOS ids) */
+  const int64_t* forced_ids;   /* [n_forced]: the ids that read 0 on a UVX_BAN_FORCED step */
+  const int64_t* suppress_ids; /* [n_suppress]: banned on every step */
+  const int64_t* begin_ids;    /* [n_begin]: banned while UVX_BAN_BEGIN is set */
+  int32_t ngram;               /* no_repeat_ngram_size, 0 = off */
+  int32_t n_bad, n_bad_tokens, n_min, n_forced, n_suppress, n_begin;
+} uvx_ban_rules_t;
+/* The step-dependent conditions, the same for every row; the host evaluates them per launch (L = col, the row's length before this token):
+ * MIN: L < min_length or L - prompt_len < min_new_tokens;  FORCED: forced ids are given and L == max_len - 1;  BEGIN: L == prompt_len. */
+#define UVX_BAN_MIN 1u
+#define UVX_BAN_FORCED 2u
+#define UVX_BAN_BEGIN 4u
+/* uvx_greedy_select_penalized behind the ban rules (seen == NULL: no penalty, `penalty` and `words` are then unused for it).  Row b's block first
+ * rebuilds row b of `ban` (uint32 [B][ban_words], ban_words >= ceil(V / 32), the layout of `seen`; it need not be cleared) from
+ * sequences[b, 0 .. col) in HF's processor order:
+ *   n-gram      n = ngram > 0, L = col >= n: every j in [0, L - n] whose n - 1 ids equal the row's last n - 1 bans sequences[b, j + n - 1]
+ *   bad words   a one-token entry is banned; a longer one of at most L tokens bans its last token where the row's tail equals its prefix
+ *   MIN         min_ids are banned
+ *   FORCED      everything is banned but forced_ids, and the three rules above are void (HF's fill_(-inf) overwrites them)
+ *   suppress_ids are banned on every step, begin_ids under BEGIN - after FORCED, so a forced id among them stays banned.
+ * A banned element reads -inf; on a FORCED step the others read 0.0f; otherwise they read as in uvx_greedy_select_penalized.  scores_out, the token
+ * (index 0 where nothing is above -inf), the bookkeeping and the update of `seen` are that entry point's.  Afterwards bits < V of row b of `ban`
+ * are exactly this step's banned set; higher bits are unspecified.  flags: other bits than the three above are an error.  V < 2^23. */
+int32_t uvx_greedy_select_banned(void* stream, int32_t logits_dtype, const void* logits, int32_t B, int32_t V, float penalty, uint32_t* seen,
+                                 int32_t words, float* scores_out, const uvx_ban_rules_t* rules, uint32_t flags, uint32_t* ban, int32_t ban_words,
+                                 const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished, int64_t* next_tokens, int64_t* sequences,
+                                 int64_t stride, int64_t col, const int32_t* positions0, int32_t* positions, int32_t step, int32_t* counter);
+/* uvx_sample_select_penalized behind the same rules: the warpers and the draw see the scores as uvx_greedy_select_banned reads them (processors
+ * before warpers).  seen == NULL: no penalty.  With no rule and no flag it gives uvx_sample_select's / uvx_sample_select_penalized's tokens and
+ * probabilities bit for bit. */
+int32_t uvx_sample_select_banned(void* stream, int32_t logits_dtype, const void* logits, int32_t B, int32_t V, float penalty, uint32_t* seen,
+                                 int32_t words, float temperature, int32_t top_k, float top_p, float min_p, int32_t min_keep, uint64_t seed,
+                                 uint64_t offset, const float* uniforms, float* probs_out, const uvx_ban_rules_t* rules, uint32_t flags, uint32_t* ban,
+                                 int32_t ban_words, const int64_t* eos_ids, int32_t n_eos, int64_t pad, int32_t* unfinished, int64_t* next_tokens,
+                                 int64_t* sequences, int64_t stride, int64_t col, const int32_t* positions0, int32_t* positions, int32_t step,
+                                 int32_t* counter);
 
 /* clip_grad_norm_(max_norm) + torch.optim.AdamW step over one flat parameter bucket (train.py:260,
  * config_base.py:149-154).  grad: f32 [n] (already DP-averaged).  state_dtype selects the storage of

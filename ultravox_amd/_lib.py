@@ -214,6 +214,15 @@ class LlmWeights(C.Structure):
                 ("rope_len", C.c_int32), ("rope_cos_sin_local", C.c_void_p), ("layer_local", C.POINTER(C.c_int32))]
 
 
+class BanRules(C.Structure):      # uvx_ban_rules_t: device pointers and counts of one generate() call's token-ban rules
+    _fields_ = [("bad_tokens", C.c_void_p), ("bad_offsets", C.c_void_p), ("min_ids", C.c_void_p), ("forced_ids", C.c_void_p),
+                ("suppress_ids", C.c_void_p), ("begin_ids", C.c_void_p), ("ngram", C.c_int32), ("n_bad", C.c_int32), ("n_bad_tokens", C.c_int32),
+                ("n_min", C.c_int32), ("n_forced", C.c_int32), ("n_suppress", C.c_int32), ("n_begin", C.c_int32)]
+
+
+BAN_MIN, BAN_FORCED, BAN_BEGIN = 1, 2, 4      # UVX_BAN_*: the per-step flag word of the banned selectors
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
                 ("kv_start", C.c_void_p), ("kv_len", C.c_void_p),
@@ -230,7 +239,7 @@ EXPORTS = [
     "uvx_llm_ws_bytes", "uvx_llm_fwd", "uvx_llm_bwd", "uvx_adamw_clip_step", "uvx_gemm", "uvx_layernorm",
     "uvx_rmsnorm", "uvx_gemm_rmsnorm", "uvx_rmsnorm_bwd", "uvx_swiglu", "uvx_swiglu_bwd", "uvx_rope", "uvx_qk_norm_rope", "uvx_qk_norm_bwd", "uvx_attention_ws_bytes",
     "uvx_attention_fwd", "uvx_attention_bwd", "uvx_ce_loss", "uvx_prof_begin", "uvx_prof_enable", "uvx_prof_end", "uvx_prof_records", "uvx_prof_union_ms", "uvx_probe_lds_tr", "uvx_gemm_force_variant", "uvx_attention_force_qt", "uvx_kv_cache_bytes", "uvx_llm_infer_ws_bytes",
-    "uvx_llm_prefill", "uvx_llm_prefill_chunk", "uvx_llm_prefill_chunk_logits", "uvx_llm_prefill_chunk_ws_bytes", "uvx_llm_decode", "uvx_argmax", "uvx_greedy_select", "uvx_sample_select", "uvx_seen_mark", "uvx_greedy_select_penalized", "uvx_sample_select_penalized", "uvx_llm_kl_loss", "uvx_kl_loss", "uvx_gemm_override_variant", "uvx_gemm_pick_variant", "uvx_set_option", "uvx_get_option",
+    "uvx_llm_prefill", "uvx_llm_prefill_chunk", "uvx_llm_prefill_chunk_logits", "uvx_llm_prefill_chunk_ws_bytes", "uvx_llm_decode", "uvx_argmax", "uvx_greedy_select", "uvx_sample_select", "uvx_seen_mark", "uvx_greedy_select_penalized", "uvx_sample_select_penalized", "uvx_greedy_select_banned", "uvx_sample_select_banned", "uvx_llm_kl_loss", "uvx_kl_loss", "uvx_gemm_override_variant", "uvx_gemm_pick_variant", "uvx_set_option", "uvx_get_option",
     "uvx_encoder_train_ws_bytes", "uvx_encoder_fwd_train", "uvx_encoder_bwd", "uvx_layernorm_bwd", "uvx_gelu", "uvx_gelu_bwd",
     "uvx_llm_fwd_rows", "uvx_llm_kl_loss_rows", "uvx_llm_bwd_rows", "uvx_llm_bwd_rows_from", "uvx_llm_fwd_lora", "uvx_llm_bwd_lora",
     "uvx_llm_fwd_train", "uvx_llm_bwd_train", "uvx_llm_bwd_train_from",
@@ -263,3 +272,7 @@ def _declare(l: C.CDLL) -> None:
     l.uvx_greedy_select_penalized.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, vp, vp, i32, i64, vp, vp, vp, i64, i64, vp, vp, i32, vp]
     l.uvx_sample_select_penalized.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, f32, i32, f32, f32, i32, u64, u64, vp, vp, vp, i32, i64, vp, vp, vp, i64, i64,
                                               vp, vp, i32, vp]
+    u32 = C.c_uint32
+    book = [vp, i32, i64, vp, vp, vp, i64, i64, vp, vp, i32, vp]
+    l.uvx_greedy_select_banned.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, vp, vp, u32, vp, i32, *book]
+    l.uvx_sample_select_banned.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, f32, i32, f32, f32, i32, u64, u64, vp, vp, vp, u32, vp, i32, *book]

@@ -10,6 +10,10 @@ through the oracle.
 Order (HF's): repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, forced_eos_token_id, suppress_tokens,
 begin_suppress_tokens, then the caller's own `logits_processor` callables; sampling adds temperature -> top_k -> top_p -> min_p (model.py `_sample`).
 Keywords of HF's generation config that would change the tokens and are NOT built raise instead of being ignored.
+
+The repetition penalty and the seven token-ban processors also exist as kernels (uvx_greedy_select_penalized / uvx_greedy_select_banned and their
+sampling twins, include/uvx.h): where every active processor is one of those, model.py's device loop takes them and `ScoreProcessors` only hands it
+the rule lists (`device_rules`) and the per-step flags (`step_flags`); the restatements below stay the host loop's and the beam search's.
 """
 from typing import Callable, List, Optional, Sequence
 
@@ -97,11 +101,15 @@ class PhiloxGenerator:
     counter's low 64 bits (`offset`).  Decode step s of a generate() call draws row b's uniform from counter (offset + s, b); the call then
     advances the offset by the steps it ran, so consecutive calls never reuse a counter and a (seed, offset) pair replays a call.
     penalty_on_device=True additionally lets generate() take a `repetition_penalty` that is the only score processor onto the device
-    (uvx_seen_mark + uvx_sample_select_penalized); without the flag that combination is refused, as every other processor is either way."""
+    (uvx_seen_mark + uvx_sample_select_penalized); without the flag that combination is refused.  processors_on_device=True implies it and also
+    takes the token-ban processors (no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, forced_eos_token_id, suppress_tokens,
+    begin_suppress_tokens, alone or next to the penalty) onto the device (uvx_sample_select_banned); without that flag they are refused, and a
+    caller's own `logits_processor` is refused either way."""
     MASK = (1 << 64) - 1
 
-    def __init__(self, seed: int = 0, penalty_on_device: bool = False):
-        self.penalty_on_device = bool(penalty_on_device)
+    def __init__(self, seed: int = 0, penalty_on_device: bool = False, processors_on_device: bool = False):
+        self.processors_on_device = bool(processors_on_device)
+        self.penalty_on_device = bool(penalty_on_device) or self.processors_on_device
         self.manual_seed(seed)
 
     def manual_seed(self, seed: int) -> "PhiloxGenerator":
@@ -170,6 +178,42 @@ class ScoreProcessors:
         """The repetition penalty is the one active processor: what uvx_greedy_select_penalized and uvx_sample_select_penalized do on the device."""
         return bool(self.rep is not None and not (self.ngram or self.bad_words or self.min_length > 0 or self.min_new > 0 or self.forced_eos
                                                   or self.suppress or self.begin_suppress or self.user))
+
+    # ---- the same rule set for the banned selectors (uvx_greedy_select_banned / uvx_sample_select_banned, include/uvx.h) ----
+    @property
+    def bans(self) -> bool:
+        """One of the seven token-ban processors is active."""
+        return bool(self.ngram or self.bad_words or self.min_length > 0 or self.min_new > 0 or self.forced_eos or self.suppress or self.begin_suppress)
+
+    def _kept_bad_words(self) -> List[List[int]]:
+        eos = set(self.eos)
+        return [list(map(int, w)) for w in self.bad_words if not (len(w) == 1 and int(w[0]) in eos)]      # (as bad_words_ drops them)
+
+    def on_device(self, vocab: int) -> bool:
+        """Every active processor is one the banned selectors express: a ban rule is active, no caller `logits_processor`, and every listed id lies
+        in [0, vocab) (torch indexes with the others - wrapping or raising; that stays the host loop's business)."""
+        listed = [t for w in self._kept_bad_words() for t in w] + self.forced_eos + self.suppress + self.begin_suppress
+        return bool(self.bans and not self.user and all(0 <= t < vocab for t in listed))
+
+    def device_rules(self, device) -> dict:
+        """The rule lists uploaded once per generate() call: the fields of uvx_ban_rules_t, the pointers as tensors (None for an empty list)."""
+        def ids(v, dtype=torch.int64):
+            return torch.tensor(v, device=device, dtype=dtype) if len(v) else None
+        words = self._kept_bad_words()
+        offsets = [0]
+        for w in words:
+            offsets.append(offsets[-1] + len(w))
+        min_ids = [e for e in self.eos if e >= 0] if (self.min_length > 0 or self.min_new > 0) else []
+        return dict(bad_tokens=ids([t for w in words for t in w]), bad_offsets=ids(offsets, torch.int32) if words else None, min_ids=ids(min_ids),
+                    forced_ids=ids(self.forced_eos), suppress_ids=ids(self.suppress), begin_ids=ids(self.begin_suppress), ngram=self.ngram,
+                    n_bad=len(words), n_bad_tokens=offsets[-1], n_min=len(min_ids), n_forced=len(self.forced_eos), n_suppress=len(self.suppress),
+                    n_begin=len(self.begin_suppress))
+
+    def step_flags(self, L: int) -> int:
+        """The step-dependent conditions of __call__ for a row of length L (the same for every row): UVX_BAN_MIN | UVX_BAN_FORCED | UVX_BAN_BEGIN."""
+        short = (self.min_length > 0 and L < self.min_length) or (self.min_new > 0 and L - self.prompt_len < self.min_new)
+        return ((1 if short and any(e >= 0 for e in self.eos) else 0) | (2 if self.forced_eos and L == self.max_len - 1 else 0)
+                | (4 if self.begin_suppress and L == self.prompt_len else 0))
 
     def __call__(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
         L = ids.shape[1]

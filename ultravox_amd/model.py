@@ -130,6 +130,9 @@ class UltravoxModel:
     # generate(): greedy decoding under a repetition penalty alone selects its tokens on the device (uvx_greedy_select_penalized).  __init__ turns it
     # on; False keeps the host loop (generation.repetition_penalty_ + argmax on f32 scores) - also for an object that never ran __init__
     penalized_select = False
+    # ... and under the token-ban score processors, alone or next to the penalty (uvx_greedy_select_banned), the same way: False keeps the host loop
+    # (generation.ScoreProcessors.__call__ + argmax on f32 scores)
+    banned_select = False
 
     def __init__(self, config: UltravoxConfig, state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  device: str = "cuda", dtype: Optional[torch.dtype] = None, seed: int = 0,
@@ -155,6 +158,7 @@ class UltravoxModel:
         # training step: last layer's o_proj / MLP on the supervised rows only (uvx_llm_fwd_train); A/B switch for the probes
         self.top_layer_supervised_rows = os.environ.get("UVX_TOP_LAYER_ROWS", "1") != "0"
         self.penalized_select = True             # (class attribute above)
+        self.banned_select = True                # (likewise)
         self._llm_train_pair = False             # which uvx_llm_bwd* entry point pairs with the last language_model_forward
         self._llm_top_rows = False
         self._kl_grad_scale = 1.0
@@ -1139,10 +1143,22 @@ class UltravoxModel:
         procs = generation.ScoreProcessors(kwargs, T, max_new_tokens, eos_list, rep)
         # a PhiloxGenerator selects the device sampler (uvx_sample_select): warpers, draw and bookkeeping in one launch per token.  What that kernel
         # does not do keeps the torch path for now and is refused by name instead of being sampled some other way.  A generator made with
-        # penalty_on_device=True also takes a repetition penalty that is the only score processor (uvx_sample_select_penalized).
+        # penalty_on_device=True also takes a repetition penalty that is the only score processor (uvx_sample_select_penalized), one made with
+        # processors_on_device=True the token-ban processors too, alone or next to the penalty (uvx_sample_select_banned).
         philox = generator if do_sample and isinstance(generator, generation.PhiloxGenerator) else None
         sampled_penalized = bool(philox is not None and philox.penalty_on_device and procs.only_repetition_penalty and rep <= 3.4e38)
-        if philox is not None:
+        bans_fit = procs.on_device(V) and (rep is None or rep <= 3.4e38)      # (the kernel's penalty is a finite f32)
+        sampled_banned = bool(philox is not None and philox.processors_on_device and bans_fit)
+        if philox is not None and philox.processors_on_device:
+            clash = [n for n, on in (("logits_processor", bool(procs.user)),
+                                     ("score processors that list ids outside the vocabulary, or a repetition_penalty that is no finite f32",
+                                      procs.active and not procs.user and not sampled_penalized and not sampled_banned),
+                                     ("stopping_criteria", bool(crit)), ("output_logits", bool(kwargs.get("output_logits", False))),
+                                     ("num_beams > 1", num_beams > 1)) if on]
+            if clash:
+                raise ValueError(f"generate(): a PhiloxGenerator (the device sampler) cannot be combined with {'; '.join(clash)}: pass a "
+                                 "torch.Generator or no generator for these")
+        elif philox is not None:
             clash = [n for n, on in (("score processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens, "
                                       "forced_eos_token_id, suppress_tokens, begin_suppress_tokens, logits_processor)", procs.active and not sampled_penalized),
                                      ("stopping_criteria", bool(crit)), ("output_logits", bool(kwargs.get("output_logits", False))),
@@ -1208,17 +1224,22 @@ class UltravoxModel:
         n_decoded = 0
         # The device loop: choosing the token and the loop's per-token bookkeeping - pad once a sequence has finished, the EOS test, the next RoPE
         # position - are ONE launch and one 4-byte read-back instead of argmax + eight small torch kernels (profiles/r05_decode70_b8_kernel_stats.txt
-        # lists them as at::native rows).  Same tokens.  Its four variants are reader x chooser of csrc/select.hip:
+        # lists them as at::native rows).  Same tokens.  Its variants are reader x chooser of csrc/select.hip and csrc/select_banned.hip:
         #   greedy, no score processor (the BASELINE inference configuration)                        uvx_greedy_select
         #   greedy under a repetition penalty alone (the reference pipeline's default call)          uvx_greedy_select_penalized
         #   sampling under a PhiloxGenerator: decode step s draws from counter offset + s            uvx_sample_select
         #   ... with penalty_on_device=True and a repetition penalty alone                           uvx_sample_select_penalized
+        #   greedy under the token-ban processors, alone or next to the penalty                      uvx_greedy_select_banned
+        #   ... sampling, with processors_on_device=True                                             uvx_sample_select_banned
         # The penalised ones read the ids of the row from a bitmap that uvx_seen_mark fills once from the WHOLE input_ids - left padding, audio
         # placeholders and a prefix that past_key_values covers included, as HF penalises every id of the row - and the kernel extends per token.
+        # The banned ones rebuild a second bitmap, the step's banned ids, inside every launch from the row so far (`seq` holds the whole input_ids
+        # too), the rule lists uploaded once (generation.ScoreProcessors.device_rules) and a flag word for the step's conditions (step_flags).
         device_loop = not crit and not do_sample and not want_logits and os.environ.get("UVX_GREEDY_SELECT", "1") != "0"
         greedy = not procs.active and device_loop
         penalized = procs.only_repetition_penalty and self.penalized_select and device_loop and rep <= 3.4e38      # (the kernel's penalty is a finite f32)
-        if greedy or penalized or philox is not None:
+        banned = bans_fit and self.banned_select and device_loop
+        if greedy or penalized or banned or philox is not None:
             seq = torch.empty(B, T + max_new_tokens, device=dev, dtype=torch.int64)
             seq[:, :T] = ids_dev
             live = torch.ones(B, device=dev, dtype=torch.int32)
@@ -1228,18 +1249,26 @@ class UltravoxModel:
             # the entry point and its arguments between V and the bookkeeping: how the row is read, then how the token is chosen
             name = "uvx_sample_select" if philox is not None else "uvx_greedy_select"
             pen = ()
-            if penalized or sampled_penalized:
-                name += "_penalized"
-                words = (V + 31) // 32
+            words = (V + 31) // 32
+            with_bans = banned or sampled_banned
+            if penalized or sampled_penalized or (with_bans and rep is not None):
                 seen = torch.zeros(B, words, device=dev, dtype=torch.int32)
                 ids64 = ids_dev if ids_dev.dtype == torch.int64 and (T == 1 or ids_dev.stride(1) == 1) else ids_dev.to(torch.int64).contiguous()
                 check(l.uvx_seen_mark(stream_ptr(), ptr(ids64), C.c_int64(ids64.stride(0)), B, T, V, ptr(seen), words), "uvx_seen_mark")
                 pen = (float(rep), ptr(seen), words)
+            name += "_banned" if with_bans else "_penalized" if pen else ""
+            bans = lambda step: ()
+            if with_bans:                      # (no penalty: a null bitmap)
+                pen = pen or (1.0, None, 0)
+                lists = procs.device_rules(dev)
+                rules = _lib.BanRules(**{f: ptr(v) if isinstance(v, torch.Tensor) else v for f, v in lists.items()})
+                ban = torch.empty(B, words, device=dev, dtype=torch.int32)
+                bans = lambda step: (C.byref(rules), procs.step_flags(T + step), ptr(ban), words)
             if philox is not None:             # (no uniforms, no probs_out)
                 warp = (float(temperature), int(top_k or 0), 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p), 1, philox.seed)
-                head = lambda step: (*pen, *warp, (philox.offset + step) & philox.MASK, None, None)
+                head = lambda step: (*pen, *warp, (philox.offset + step) & philox.MASK, None, None, *bans(step))
             else:                              # (no scores_out)
-                head = lambda step: (*pen, None) if pen else ()
+                head = lambda step: (*pen, None, *bans(step)) if pen else ()
             book = lambda step: (ptr(eos_ids), len(eos_list), C.c_int64(int(pad)), ptr(live), ptr(nxt), ptr(seq), C.c_int64(seq.stride(0)),
                                  C.c_int64(T + step), ptr(next_pos), ptr(pos), step, ptr(counter))
             select = getattr(l, name)

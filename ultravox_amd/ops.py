@@ -335,6 +335,64 @@ def sample_select_penalized(logits, seen, penalty, *, temperature=1.0, top_k=0, 
     return dict(out, probs=probs, seen=seen)
 
 
+def ban_rules(device, *, ngram=0, bad_words=(), min_ids=(), forced_ids=(), suppress_ids=(), begin_ids=()):
+    """The rules of the banned selectors on `device`: -> (uvx_ban_rules_t mirror, the tensors its pointers refer to - keep them alive with it).
+    bad_words: a list of id lists, flattened to tokens + offsets (lone-EOS entries are the caller's to drop, as generation.ScoreProcessors does)."""
+    def ids(v, dtype=torch.int64):
+        return torch.tensor(list(map(int, v)), device=device, dtype=dtype) if len(v) else None
+    offsets = [0]
+    for w in bad_words:
+        offsets.append(offsets[-1] + len(w))
+    t = dict(bad_tokens=ids([t for w in bad_words for t in w]), bad_offsets=ids(offsets, torch.int32) if len(bad_words) else None, min_ids=ids(min_ids),
+             forced_ids=ids(forced_ids), suppress_ids=ids(suppress_ids), begin_ids=ids(begin_ids))
+    rules = _lib.BanRules(**{k: ptr(v) for k, v in t.items()}, ngram=int(ngram), n_bad=len(bad_words), n_bad_tokens=offsets[-1], n_min=len(min_ids),
+                          n_forced=len(forced_ids), n_suppress=len(suppress_ids), n_begin=len(begin_ids))
+    return rules, t
+
+
+def _ban_args(name, logits, seen, rules, ban):
+    B, V = logits.shape
+    if seen is not None:
+        _check_seen(name, seen, B)
+    if ban is None:
+        ban = torch.empty(B, seen_words(V), device=logits.device, dtype=torch.int32)
+    _check_seen(name, ban, B)
+    if isinstance(rules, tuple):
+        rules = rules[0]
+    return ban, (C.byref(rules),), (ptr(seen), 0 if seen is None else seen.shape[1])
+
+
+def greedy_select_banned(logits, rules, flags=0, *, seen=None, penalty=1.0, ban=None, want_scores=False, eos_ids=None, pad=0, unfinished=None,
+                         sequences=None, col=0, positions0=None, step=0, counter=None):
+    """uvx_greedy_select_banned on a [B, V] logits matrix (include/uvx.h): rules from ban_rules(), flags the step's UVX_BAN_* word, `sequences` the
+    rows the n-gram and bad-word rules read (columns below `col`); seen / penalty as greedy_select_penalized (None: no penalty); `ban` int32
+    [B, words] (created if not given, rewritten by the launch).  greedy_select_penalized's dict plus `ban`."""
+    B, V = logits.shape
+    ban, rl, pen = _ban_args("greedy_select_banned", logits, seen, rules, ban)
+    logits = logits.contiguous()
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    scores = torch.empty(B, V, device=logits.device, dtype=torch.float32) if want_scores else None
+    check(_lib.lib().uvx_greedy_select_banned(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), *pen, ptr(scores), *rl, int(flags), ptr(ban),
+                                              ban.shape[1], *book), "uvx_greedy_select_banned")
+    return dict(out, scores=scores, seen=seen, ban=ban)
+
+
+def sample_select_banned(logits, rules, flags=0, *, seen=None, penalty=1.0, ban=None, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, min_keep=1, seed=0,
+                         offset=0, uniforms=None, want_probs=False, eos_ids=None, pad=0, unfinished=None, sequences=None, col=0, positions0=None, step=0,
+                         counter=None):
+    """uvx_sample_select_banned on a [B, V] logits matrix: greedy_select_banned's rule arguments, sample_select's keywords and its dict, plus
+    `seen` and `ban`."""
+    B, V = logits.shape
+    ban, rl, pen = _ban_args("sample_select_banned", logits, seen, rules, ban)
+    logits = logits.contiguous()
+    out, book = _select_book(logits, eos_ids, pad, unfinished, sequences, col, positions0, step, counter)
+    probs = torch.empty(B, V, device=logits.device, dtype=torch.float32) if want_probs else None
+    check(_lib.lib().uvx_sample_select_banned(stream_ptr(), _code(logits), ptr(logits), B, V, float(penalty), *pen, float(temperature), int(top_k),
+                                              float(top_p), float(min_p), int(min_keep), int(seed), int(offset), ptr(uniforms), ptr(probs), *rl, int(flags),
+                                              ptr(ban), ban.shape[1], *book), "uvx_sample_select_banned")
+    return dict(out, probs=probs, seen=seen, ban=ban)
+
+
 # ---- polyphase resampling (uvx_resample_poly) ----
 RESAMPLE_TILE = 256          # outputs of one row per block: TILE of csrc/resample.h (the tests put n_out on either side of it)
 RESAMPLE_MAX_RATIO = 1024    # up and down are each at most this: MAX_RATIO of csrc/resample.h
