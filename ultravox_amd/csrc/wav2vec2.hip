@@ -23,6 +23,7 @@ using namespace uvx;
 
 constexpr int K0P = 64;     // the first conv's kernel (10 taps) zero padded to one GEMM K-tile
 constexpr int GN_ROWS = 512;  // time rows per GroupNorm partial block
+constexpr size_t WS_TAIL = 256;  // what uvx_wav2vec2_ws_bytes / _train_ws_bytes report past the last buffer; the entry points ask for all of it
 
 // out[(b T0 + t), k] = round(in[b, s t + k]) for k < k0, 0 for k0 <= k < 64
 template <typename T, typename TIN>
@@ -44,36 +45,82 @@ __global__ void w2v_im2col0_k(const TIN* __restrict__ in, T* __restrict__ out, l
 }
 
 // GroupNorm(num_groups = C): per (clip, channel) statistics over the T0 frames of a time-major [B, T0, C] tensor.
-// pass 1: each block sums GN_ROWS rows for all channels (thread = 8 channels); pass 2: combines the chunks in double.
+// pass 1: each block takes GN_ROWS rows for all channels and leaves the chunk's (mean, sum of squared deviations from it); pass 2: merges the chunks
+// in double.  A chunk is walked twice: a plain sum gives its rough mean, then the sums run over the deviations from that.  E[x^2] - mean^2 over
+// plain sums loses the variance of a channel whose offset is many times its spread over time (a conv bias of 10 .. 30 spreads, 1799 rows, f32: rstd
+// off by 6e-5 .. 1e-4); deviations from the chunk's first row would lose it the same way where that row is an outlier.
+// Block = (C / 8, ny): thread (tx, ty) walks rows r0 + ty, r0 + ty + ny, .. of 8 channels; the ny partial sums of a channel meet in LDS (red: ny C
+// floats) and are added in the order of ty by every thread alike.
 template <typename T>
 __global__ void w2v_gn_partial_k(const T* __restrict__ x, float* __restrict__ part, int T0, int C, int nchunk) {
-  const int b = blockIdx.y, ch = blockIdx.x;
+  extern __shared__ float red[];
+  const int b = blockIdx.y, ch = blockIdx.x, ty = threadIdx.y, ny = blockDim.y;
   const int c = threadIdx.x * 8;
-  if (c >= C) return;
   const int r0 = ch * GN_ROWS, r1 = min(T0, r0 + GN_ROWS);
-  const T* p = x + ((long long)b * T0 + r0) * C + c;
-  float s[8], q[8];
+  const T* p0 = x + ((long long)b * T0 + r0 + ty) * C + c;
+  const float inv_n = 1.f / (float)(r1 - r0);
+  float m[8], s[8], q[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
-  for (int r = r0; r < r1; ++r, p += C) {
+  for (int j = 0; j < 8; ++j) { m[j] = 0.f; s[j] = 0.f; q[j] = 0.f; }
+  const T* p = p0;
+  for (int r = r0 + ty; r < r1; r += ny, p += (long long)ny * C) {
     float v[8];
     ld8<T>(p, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+    for (int j = 0; j < 8; ++j) m[j] += v[j];
   }
+  auto block_sum = [&](float* a) {      // a[j] <- the sum over ty of a[j], the same bits in every thread of the channel
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[ty * C + c + j] = a[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = 0.f;
+      for (int y = 0; y < ny; ++y) t += red[y * C + c + j];
+      a[j] = t;
+    }
+    __syncthreads();
+  };
+  block_sum(m);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m[j] *= inv_n;
+  p = p0;
+  for (int r = r0 + ty; r < r1; r += ny, p += (long long)ny * C) {
+    float v[8];
+    ld8<T>(p, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float dv = v[j] - m[j];
+      s[j] += dv; q[j] += dv * dv;
+    }
+  }
+  block_sum(s);
+  block_sum(q);
+  if (ty != 0) return;
   float* o = part + (((long long)b * nchunk + ch) * C + c) * 2;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { o[2 * j] = s[j]; o[2 * j + 1] = q[j]; }
+  for (int j = 0; j < 8; ++j) {
+    o[2 * j] = m[j] + s[j] * inv_n;
+    o[2 * j + 1] = fmaxf(q[j] - s[j] * s[j] * inv_n, 0.f);
+  }
+}
+// rows of a chunk that one block walks side by side: as many as 1024 threads allow, 8 at the most
+inline int gn_lanes(int C) {
+  const int n = 1024 / (C / 8);
+  return n < 1 ? 1 : n > 8 ? 8 : n;
 }
 __global__ void w2v_gn_final_k(const float* __restrict__ part, float* __restrict__ stat, int T0, int C, int nchunk, float eps) {
   const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double s = 0., q = 0.;
-  for (int ch = 0; ch < nchunk; ++ch) {
+  double n = 0., mean = 0., m2 = 0.;
+  for (int ch = 0; ch < nchunk; ++ch) {      // the pairwise update of (count, mean, sum of squared deviations)
     const float* p = part + (((long long)b * nchunk + ch) * C + c) * 2;
-    s += p[0]; q += p[1];
+    const double nb = min(GN_ROWS, T0 - ch * GN_ROWS), delta = (double)p[0] - mean, nt = n + nb;
+    mean += delta * nb / nt;
+    m2 += (double)p[1] + delta * delta * n * nb / nt;
+    n = nt;
   }
-  const double mean = s / T0, var = fmax(q / T0 - mean * mean, 0.);   // biased variance, as torch.nn.GroupNorm
+  const double var = m2 / T0;   // biased variance, as torch.nn.GroupNorm
   stat[((long long)b * C + c) * 2] = (float)mean;
   stat[((long long)b * C + c) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
@@ -217,7 +264,7 @@ extern "C" size_t uvx_wav2vec2_ws_bytes(const uvx_w2v_config_t* cfg, int32_t B, 
   if (!cfg) return 0;
   Arena a(nullptr, 0);
   carve(a, *cfg, B, L);
-  return a.off + 256;
+  return a.off + WS_TAIL;
 }
 
 // lora != NULL: the LoRA-training forward (apply_lora on the AutoModel tower, ultravox_model.py:460-467, 690-709) - adapters on the attention
@@ -240,7 +287,7 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
   Arena a(workspace, ws_bytes);
   W2vWs s = carve(a, c, B, L, train);
   UVX_CHECK(s.Tn > 0, UVX_ERR_SHAPE, "wav2vec2_fwd: %d samples are shorter than the conv stack's receptive field", L);
-  UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "wav2vec2_fwd: workspace %zu < %zu bytes", ws_bytes, a.off);
+  UVX_CHECK(ws_bytes >= a.off + WS_TAIL, UVX_ERR_WORKSPACE, "wav2vec2_fwd: workspace %zu < %zu bytes", ws_bytes, a.off + WS_TAIL);
   const int dt = c.dtype, C = c.conv_dim, d = c.d, M = B * s.Tn, Tn = s.Tn;
   const EncStackDesc D = stack_desc(c, B, Tn, train);
   UVX_CHECK(dt == DT_BF16 || values_is_f32, UVX_ERR_INVALID, "wav2vec2_fwd: f32 mode needs f32 input_values");
@@ -266,11 +313,11 @@ static int w2v_forward(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_
       RC(layernorm_fwd(st, dt, s.bufA, w->conv_ln_w[0], w->conv_ln_b[0], s.bufA, (int)rows, C, 1e-5f));
       RC(gelu_fwd(st, dt, s.bufA, s.bufA, rows * C));
     } else if (dt == DT_BF16) {      // GroupNorm over time (per clip and channel) + GELU
-      hipLaunchKernelGGL(w2v_gn_partial_k<bf16_t>, gp, dim3(C / 8), 0, st, (const bf16_t*)s.bufA, s.part, s.T[0], C, s.nchunk);
+      hipLaunchKernelGGL(w2v_gn_partial_k<bf16_t>, gp, dim3(C / 8, gn_lanes(C)), sizeof(float) * gn_lanes(C) * C, st, (const bf16_t*)s.bufA, s.part, s.T[0], C, s.nchunk);
       hipLaunchKernelGGL(w2v_gn_final_k, dim3(g1(C, 128), B), dim3(128), 0, st, s.part, s.stat, s.T[0], C, s.nchunk, 1e-5f);
       hipLaunchKernelGGL(w2v_gn_gelu_k<bf16_t>, dim3(g1(n8, 256)), dim3(256), 0, st, (bf16_t*)s.bufA, s.stat, (const bf16_t*)w->gn_w, (const bf16_t*)w->gn_b, n8, s.T[0], C);
     } else {
-      hipLaunchKernelGGL(w2v_gn_partial_k<float>, gp, dim3(C / 8), 0, st, (const float*)s.bufA, s.part, s.T[0], C, s.nchunk);
+      hipLaunchKernelGGL(w2v_gn_partial_k<float>, gp, dim3(C / 8, gn_lanes(C)), sizeof(float) * gn_lanes(C) * C, st, (const float*)s.bufA, s.part, s.T[0], C, s.nchunk);
       hipLaunchKernelGGL(w2v_gn_final_k, dim3(g1(C, 128), B), dim3(128), 0, st, s.part, s.stat, s.T[0], C, s.nchunk, 1e-5f);
       hipLaunchKernelGGL(w2v_gn_gelu_k<float>, dim3(g1(n8, 256)), dim3(256), 0, st, (float*)s.bufA, s.stat, (const float*)w->gn_w, (const float*)w->gn_b, n8, s.T[0], C);
     }
@@ -344,7 +391,7 @@ extern "C" size_t uvx_wav2vec2_train_ws_bytes(const uvx_w2v_config_t* cfg, int32
   if (!cfg) return 0;
   Arena a(nullptr, 0);
   carve(a, *cfg, B, L, true);
-  return a.off + 256;
+  return a.off + WS_TAIL;
 }
 
 extern "C" int32_t uvx_wav2vec2_fwd_train(void* stream, const uvx_w2v_config_t* cfg, const uvx_w2v_weights_t* w, const uvx_encoder_lora_t* lora,
@@ -369,7 +416,7 @@ extern "C" int32_t uvx_wav2vec2_bwd(void* stream, const uvx_w2v_config_t* cfg, c
   Arena a(workspace, ws_bytes);
   W2vWs s = carve(a, c, B, L, true);
   UVX_CHECK(s.Tn > 0, UVX_ERR_SHAPE, "wav2vec2_bwd: %d samples are shorter than the conv stack's receptive field", L);
-  UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "wav2vec2_bwd: workspace %zu < %zu bytes", ws_bytes, a.off);
+  UVX_CHECK(ws_bytes >= a.off + WS_TAIL, UVX_ERR_WORKSPACE, "wav2vec2_bwd: workspace %zu < %zu bytes", ws_bytes, a.off + WS_TAIL);
   EncStackDesc D = stack_desc(c, B, s.Tn, true);
   D.who = "wav2vec2_bwd";
   if (c.stable_ln) {
