@@ -5,10 +5,10 @@
 // decode loop over a KV cache.  With an attention_mask HF derives position ids as cumsum(mask) - 1
 // (1 where masked) — left-padded batches (infer.py:155-194) start counting at their first real token.
 //
-// The prefill reuses the training-path kernels (no stashes).  The decode step is weight streaming and launch-bound and has
-// its own kernels: gemm_skinny.hip (M <= 16) and attn_decode_grp_k below (one block per sequence and KV head).  A further
-// chunk of tokens on top of a filled cache (conversation turns) goes through uvx_llm_prefill_chunk.
-// KV cache layout: [layer][k | v][B][Tmax][kv_heads * head_dim], caller-owned.
+// uvx_llm_prefill, uvx_llm_prefill_chunk(_logits) (a further chunk of tokens on top of a filled cache: conversation turns) and uvx_llm_decode
+// share ONE layer walk, infer_layers; each holds its checks, workspace carve, positions, attention step and head.  The prefills
+// reuse the training-path kernels (no stashes); the decode step is weight streaming and launch-bound and has its own: gemm_skinny.hip (M <= 16)
+// and attn_decode_grp_k below (one block per sequence and KV head).  KV cache: [layer][k | v][B][Tmax][kv_heads * head_dim], caller-owned.
 #include <algorithm>
 #include "host_util.h"
 #include "llm_rules.h"
@@ -78,6 +78,11 @@ __global__ void kv_append_k(const T* __restrict__ qkv, T* __restrict__ cache_k, 
   st8<T>(cache_k + dst, k);
   st8<T>(cache_v + dst, v);
 }
+void launch_kv_append(hipStream_t st, int dt, const void* qkv, void* ck, void* cv, int B, int Tn, int Tmax, int t0, int QKV, int koff, int KVD) {
+  const dim3 grid(cdiv((long long)B * Tn * (KVD / 8), 256));
+  if (dt == DT_BF16) hipLaunchKernelGGL(kv_append_k<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)ck, (bf16_t*)cv, B, Tn, Tmax, t0, QKV, koff, KVD);
+  else hipLaunchKernelGGL(kv_append_k<float>, grid, dim3(256), 0, st, (const float*)qkv, (float*)ck, (float*)cv, B, Tn, Tmax, t0, QKV, koff, KVD);
+}
 
 // Rotary embedding and cache append in ONE launch (round 4, decode: rope_k + kv_append_k were two 4.6 us launches per layer, 0.7 ms of a
 // 26 ms Llama-3.3-70B token; round 5: the prefill's Tn new positions per sequence go the same way - the pair re-read the k rows it had
@@ -124,13 +129,12 @@ __global__ void rope_kv_append_k(T* __restrict__ qkv, const float* __restrict__ 
     st8<T>(kc + D / 2 + c, ohi);
   }
 }
-// q | k | v projection, rotary embedding and cache append of Tn new positions per sequence (prefill, chunked prefill).  bf16 without
-// per-head q / k norms: the projection, then rope_kv_append_k; otherwise qkv_rope + kv_append_k (option 15 = 0 forces that pair: A/B)
-template <typename T>
+// bf16 without per-head q / k norms (rope_fusable): the only form in which the raw q | k | v rows reach it - with q / k norms or in f32 qkv_rope
+// rotates and kv_append_k appends (option 16 = 0 forces that pair in the prefill: A/B) - so it takes no dtype and no f32 kernel is built
 void launch_rope_kv_append(hipStream_t st, void* qkv, const float* cs, const int32_t* pos, void* ck, void* cv, int B, int Tn, int Tmax, int t0,
                            int Hq, int Hkv, int dh, int QKV) {
   const long long items = (long long)B * Tn * ((Hq + Hkv) * (dh / 16) + Hkv * dh / 8);
-  hipLaunchKernelGGL(rope_kv_append_k<T>, dim3(cdiv(items, 256)), dim3(256), 0, st, (T*)qkv, cs, pos, (T*)ck, (T*)cv, B, Tn, Tmax, t0, Hq, Hkv, dh, QKV);
+  hipLaunchKernelGGL(rope_kv_append_k<bf16_t>, dim3(cdiv(items, 256)), dim3(256), 0, st, (bf16_t*)qkv, cs, pos, (bf16_t*)ck, (bf16_t*)cv, B, Tn, Tmax, t0, Hq, Hkv, dh, QKV);
 }
 
 // full[b][t][koff + c] = cache_k[b][t][c], full[b][t][koff + KVD + c] = cache_v[b][t][c] for t < Tf: the cached keys / values
@@ -150,6 +154,11 @@ __global__ void kv_gather_k(const T* __restrict__ cache_k, const T* __restrict__
   ld8<T>(cache_v + src, v);
   st8<T>(full + row * QKV + koff + c, k);
   st8<T>(full + row * QKV + koff + KVD + c, v);
+}
+void launch_kv_gather(hipStream_t st, int dt, const void* ck, const void* cv, void* full, int B, int Tf, int Tmax, int QKV, int koff, int KVD) {
+  const dim3 grid(cdiv((long long)B * Tf * (KVD / 8), 256));
+  if (dt == DT_BF16) hipLaunchKernelGGL(kv_gather_k<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)ck, (const bf16_t*)cv, (bf16_t*)full, B, Tf, Tmax, QKV, koff, KVD);
+  else hipLaunchKernelGGL(kv_gather_k<float>, grid, dim3(256), 0, st, (const float*)ck, (const float*)cv, (float*)full, B, Tf, Tmax, QKV, koff, KVD);
 }
 
 // RoPE positions of a chunk that continues each sequence: pos[b * Tn + i] = pos0[b] + i
@@ -351,9 +360,22 @@ int launch_decode_grp(hipStream_t st, size_t sh, int blocks, const bf16_t* qkv, 
                      QKV, scale, lo, hsplit, rope_cs, rope_pos);
   return UVX_OK;
 }
-
-// one decoder layer on M = B*T rows; attention supplied by the caller
-struct LayerIO { void *x_in, *x_mid; };
+// the grouped kernel's instantiations by (head_dim, query heads per block); null: none serves the shape
+using DecodeGrpFn = decltype(&launch_decode_grp<128, 1>);
+DecodeGrpFn decode_grp_of(int dh, int G) {
+  static const struct { int dh, G; DecodeGrpFn launch; } table[] = {
+      {128, 1, launch_decode_grp<128, 1>}, {128, 2, launch_decode_grp<128, 2>}, {128, 4, launch_decode_grp<128, 4>}, {128, 8, launch_decode_grp<128, 8>},
+      {64, 1, launch_decode_grp<64, 1>},   {64, 2, launch_decode_grp<64, 2>},   {64, 4, launch_decode_grp<64, 4>}};
+  for (const auto& e : table) if (e.dh == dh && e.G == G) return e.launch;
+  return nullptr;
+}
+// attn_decode_k by (storage type, head_dim): the caller has checked head_dim 64 / 128 / 256
+template <typename T>
+void attn_decode_t(hipStream_t st, int dh, const void* qkv, const void* ck, const void* cv, void* o, const int32_t* kv_start, int B, int Hq, int Hkv,
+                   int Tmax, int len, int QKV, float scale, int lo) {
+  const auto k = dh == 256 ? attn_decode_k<T, 256> : dh == 64 ? attn_decode_k<T, 64> : attn_decode_k<T, 128>;
+  hipLaunchKernelGGL(k, dim3(cdiv(B * Hq, 4)), dim3(256), 0, st, (const T*)qkv, (const T*)ck, (const T*)cv, (T*)o, kv_start, B, Hq, Hkv, Tmax, len, QKV, scale, lo);
+}
 
 // n_ready: s.n already holds post_attention_layernorm(x_mid) (attn_out's split-K reduce wrote it).  next_ln1 / next_ready: the NEXT
 // layer's input_layernorm is asked of the down projection's reduce (GemmDesc::norm_*); *next_ready says whether s.n holds it on return.
@@ -429,28 +451,87 @@ int qkv_rope(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, 
   return rope_inplace(st, dt, qkv, rope, pos, rows, T, Hq + Hkv, dh, QKV, 0);
 }
 
-// q | k | v projection, rotary embedding and cache append of Tn new positions per sequence (rows b Tn + t at positions pos[row] -> cache
-// rows t0 + t): bf16 without per-head q / k norms runs the projection and then ONE launch that rotates q / k and writes the cache rows
-// (rope_kv_append_k); everything else - and tuning option 16 = 0, for A/B - runs qkv_rope and kv_append_k.  Same values either way.
-int qkv_rope_append(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, const uvx_llm_layer_t& L, const InferWs& s, const void* n,
+// the raw q | k | v rows can be rotated where they are appended (Qwen3 / Gemma-3: q_norm / k_norm + RoPE is its own kernel)
+bool rope_fusable(const uvx_config_t& c) { return c.dtype == DT_BF16 && !c.llm_qk_norm; }
+
+// The prefills' attention step up to the attention itself: input_layernorm (unless n1_ready), q | k | v projection, rotary embedding and cache
+// append of Tn new positions per sequence (rows b Tn + t at positions pos[row] -> cache rows t0 + t).  bf16 without per-head q / k norms runs the
+// projection and then ONE launch that rotates q / k and writes the cache rows (rope_kv_append_k); everything else - and tuning option 16 = 0,
+// for A/B - runs qkv_rope and kv_append_k.  Same values either way.
+int qkv_rope_append(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, const uvx_llm_layer_t& L, const InferWs& s, bool n1_ready,
                     const int32_t* pos, int B, int Tn, int Tmax, int t0, void* ck, void* cv, int l) {
-  const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh, rows = B * Tn;
-  if (dt == DT_BF16 && !c.llm_qk_norm && uvx::opt(UVX_OPT_PREFILL_ROPE_APPEND_FUSED)) {
-    GemmDesc g = lin(n, L.wqkv, s.qkv, rows, s.QKV, c.llm_d);
+  const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, rows = B * Tn;
+  if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, rows, c.llm_d, c.rms_eps, c.llm_flavor));
+  if (rope_fusable(c) && uvx::opt(UVX_OPT_PREFILL_ROPE_APPEND_FUSED)) {
+    GemmDesc g = lin(s.n, L.wqkv, s.qkv, rows, s.QKV, c.llm_d);
     g.bias = L.bqkv;
     RC(gemm(st, dt, sk(g, s)));
-    launch_rope_kv_append<bf16_t>(st, s.qkv, rope_of(c, w, l), pos, ck, cv, B, Tn, Tmax, t0, Hq, Hkv, dh, s.QKV);
-    UVX_LAUNCH_CHECK();
-    return UVX_OK;
+    launch_rope_kv_append(st, s.qkv, rope_of(c, w, l), pos, ck, cv, B, Tn, Tmax, t0, Hq, Hkv, dh, s.QKV);
+  } else {
+    RC(qkv_rope(st, c, w, L, s.n, s.qkv, pos, rows, Tn, s.QKV, l, &s));
+    launch_kv_append(st, dt, s.qkv, ck, cv, B, Tn, Tmax, t0, s.QKV, Hq * dh, Hkv * dh);
   }
-  RC(qkv_rope(st, c, w, L, n, s.qkv, pos, rows, Tn, s.QKV, l, &s));
-  const long long na = (long long)rows * (KVD / 8);
-  if (dt == DT_BF16)
-    hipLaunchKernelGGL(kv_append_k<bf16_t>, dim3(cdiv(na, 256)), dim3(256), 0, st, (const bf16_t*)s.qkv, (bf16_t*)ck, (bf16_t*)cv, B, Tn, Tmax, t0, s.QKV, Hq * dh, KVD);
-  else
-    hipLaunchKernelGGL(kv_append_k<float>, dim3(cdiv(na, 256)), dim3(256), 0, st, (const float*)s.qkv, (float*)ck, (float*)cv, B, Tn, Tmax, t0, s.QKV, Hq * dh, KVD);
   UVX_LAUNCH_CHECK();
   return UVX_OK;
+}
+
+// Decode attention of one layer: puts the new token's K / V into cache row cur_len and leaves the attention of its query over the visible slots in
+// s.o.  s.qkv holds the layer's fresh q | k | v row of every sequence: raw when rope_fusable, otherwise already rotated by qkv_rope.  Decided here,
+// once: hsplit and G, the query heads of a KV head per block (the group is split until ~256 blocks are in flight); grp, the grouped kernel where the
+// G * len scores fit 48 KB of dynamic LDS and an instantiation serves (head_dim, G), else attn_decode_k; and who rotates and appends: the grouped
+// kernel itself (in_attn; tuning option 23 = 1 keeps the separate launch: A/B), rope_kv_append_k in front of it, or - rotated rows - kv_append_k.
+int decode_attn(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, const InferWs& s, int l, const int32_t* positions,
+                const int32_t* kv_start, void* ck, void* cv, int B, int Tmax, int cur_len) {
+  const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, Gall = Hq / Hkv, len = cur_len + 1;
+  const float scale = attn_scale_of(c);
+  const int lo = decode_first_slot(c, w, l, cur_len);      // sliding-window layer: the new token attends to the last `window` cache slots
+  int hsplit = 1;      // (powers of two that divide the group)
+  while (hsplit * 2 <= Gall && Gall % (hsplit * 2) == 0 && B * Hkv * hsplit < 256) hsplit *= 2;
+  const int G = Gall / hsplit;
+  const size_t sh = sizeof(float) * (size_t)G * len;
+  const DecodeGrpFn grp = dt == DT_BF16 && sh <= 48 * 1024 ? decode_grp_of(dh, G) : nullptr;
+  // (no Gemma-3 term: it has q / k norms, so its local layers' own table never meets the fused forms; rope_of picks the table as everywhere else)
+  const bool in_attn = grp && rope_fusable(c) && opt(UVX_OPT_DECODE_ROPE_APPEND_SEPARATE) != 1;
+  const float* rope = rope_of(c, w, l);
+  if (!rope_fusable(c)) launch_kv_append(st, dt, s.qkv, ck, cv, B, 1, Tmax, cur_len, s.QKV, Hq * dh, Hkv * dh);
+  else if (!in_attn) launch_rope_kv_append(st, s.qkv, rope, positions, ck, cv, B, 1, Tmax, cur_len, Hq, Hkv, dh, s.QKV);
+  if (grp)
+    RC(grp(st, sh, B * Hkv * hsplit, (const bf16_t*)s.qkv, (bf16_t*)ck, (bf16_t*)cv, (bf16_t*)s.o, kv_start, Hq, Hkv, Tmax, len, s.QKV, scale, lo, hsplit,
+           in_attn ? rope : nullptr, positions));
+  else
+    (dt == DT_BF16 ? attn_decode_t<bf16_t> : attn_decode_t<float>)(st, dh, s.qkv, ck, cv, s.o, kv_start, B, Hq, Hkv, Tmax, len, s.QKV, scale, lo);
+  UVX_LAUNCH_CHECK();
+  return UVX_OK;
+}
+
+// plane `v` (0: keys, 1: values) of layer l in the cache [layer][k | v][B][Tmax][kv_heads * head_dim]
+char* kv_plane(const uvx_config_t& c, void* kv_cache, int l, int v, int B, int Tmax) {
+  return at(kv_cache, (size_t)(2 * l + v) * B * Tmax * c.llm_kv_heads * c.llm_head_dim, c.dtype);
+}
+
+// The layer walk of the three entry points, on M = B * (new positions per sequence) rows in s.x.  attn(l, L, ck, cv, n1_ready) is the entry
+// point's attention step: it reads s.x - or s.n when n1_ready: the previous layer's down projection has left this layer's input_layernorm
+// there (bf16 split-K reduce) -, puts the new keys / values into the layer's cache planes and leaves the attention output in s.o.
+template <class Attn>
+int infer_layers(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, InferWs& s, int M, int B, int Tmax, void* kv_cache, Attn&& attn) {
+  bool n1_ready = false, n2_ready = false;      // s.n already holds this layer's input_layernorm / post_attention_layernorm (fused reduces)
+  for (int l = 0; l < c.llm_layers; ++l) {
+    const uvx_llm_layer_t& L = w->layers[l];
+    RC(attn(l, L, kv_plane(c, kv_cache, l, 0, B, Tmax), kv_plane(c, kv_cache, l, 1, B, Tmax), n1_ready));
+    RC(attn_out(st, c, L, s, M, s.o, s.OD, s.x, s.x2, &n2_ready));
+    RC(mlp_block(st, c, L, s, M, s.x2, s.x, n2_ready, l + 1 < c.llm_layers ? w->layers[l + 1].ln1 : nullptr, &n1_ready));
+  }
+  return UVX_OK;
+}
+
+// logits of the LAST of T positions of every sequence only (what generate() consumes): s.x row T - 1 -> s.last -> final norm -> LM head
+int head_last(hipStream_t st, const uvx_config_t& c, const uvx_llm_weights_t* w, InferWs& s, int B, int T, void* logits_last) {
+  const int dt = c.dtype, D = c.llm_d;
+  const size_t es = esz(dt);
+  UVX_HIP(hipMemcpy2DAsync(s.last, (size_t)D * es, at(s.x, (size_t)(T - 1) * D, dt), (size_t)T * D * es, (size_t)D * es, B,
+                           hipMemcpyDeviceToDevice, st));
+  RC(rmsnorm_fwd(st, dt, s.last, w->norm, s.hn, nullptr, B, D, c.rms_eps, c.llm_flavor));
+  return gemm(st, dt, lin(s.hn, w->lm_head, logits_last, B, c.vocab, D));
 }
 
 }  // namespace
@@ -480,34 +561,19 @@ extern "C" int32_t uvx_llm_prefill(void* stream, const uvx_config_t* cfg, const 
   Arena a(workspace, ws_bytes);
   InferWs s = carve(a, c, B, T);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "llm_prefill: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, D = c.llm_d, M = s.M, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh;
-  const size_t es = esz(dt);
+  const int dt = c.dtype, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads;
   hipLaunchKernelGGL(mask_positions_k, dim3(B), dim3(64), 0, st, attention_mask, s.pos, kv_start, s.kvl, next_pos, T);
   UVX_LAUNCH_CHECK();
-  RC(embed_in(st, c, s.x, inputs_embeds, M));
-  const size_t layer_stride = (size_t)2 * B * Tmax * KVD;  // elements
-  bool n1_ready = false, n2_ready = false;      // s.n already holds this layer's input_layernorm / post_attention_layernorm (fused reduces)
-  for (int l = 0; l < c.llm_layers; ++l) {
-    const uvx_llm_layer_t& L = w->layers[l];
-    if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, M, D, c.rms_eps, c.llm_flavor));
-    {
-      char* ck = at(kv_cache, l * layer_stride, dt);
-      char* cv = at(kv_cache, l * layer_stride + (size_t)B * Tmax * KVD, dt);
-      RC(qkv_rope_append(st, c, w, L, s, s.n, s.pos, B, T, Tmax, 0, ck, cv, l));
-    }
+  RC(embed_in(st, c, s.x, inputs_embeds, s.M));
+  RC(infer_layers(st, c, w, s, s.M, B, Tmax, kv_cache, [&](int l, const uvx_llm_layer_t& L, void* ck, void* cv, bool n1_ready) -> int {
+    RC(qkv_rope_append(st, c, w, L, s, n1_ready, s.pos, B, T, Tmax, 0, ck, cv, l));
     if (attention_needs_transposed_copies(dt)) RC(heads_transpose(st, dt, at(s.qkv, (size_t)(Hq + Hkv) * dh, dt), s.vt, B, T, s.Tp, Hkv, dh, s.QKV));
     AttnDesc ad = causal_gqa_desc(c, s.qkv, B, T, s.Tp, s.QKV, s.OD);
     ad.vt = s.vt; ad.o = s.o; ad.kv_start = kv_start; ad.kv_len = s.kvl;
     ad.window = window_of(c, w, l, T);
-    RC(attention_fwd(st, dt, ad));
-    RC(attn_out(st, c, L, s, M, s.o, s.OD, s.x, s.x2, &n2_ready));
-    RC(mlp_block(st, c, L, s, M, s.x2, s.x, n2_ready, l + 1 < c.llm_layers ? w->layers[l + 1].ln1 : nullptr, &n1_ready));
-  }
-  // logits of the LAST position of every sequence only (what generate() consumes)
-  UVX_HIP(hipMemcpy2DAsync(s.last, (size_t)D * es, at(s.x, (size_t)(T - 1) * D, dt), (size_t)T * D * es, (size_t)D * es, B,
-                           hipMemcpyDeviceToDevice, st));
-  RC(rmsnorm_fwd(st, dt, s.last, w->norm, s.hn, nullptr, B, D, c.rms_eps, c.llm_flavor));
-  return gemm(st, dt, lin(s.hn, w->lm_head, logits_last, B, c.vocab, D));
+    return attention_fwd(st, dt, ad);
+  }));
+  return head_last(st, c, w, s, B, T, logits_last);
 }
 
 namespace {
@@ -555,25 +621,15 @@ static int32_t prefill_chunk_impl(void* stream, const uvx_config_t* cfg, const u
   ChunkWs k;
   InferWs s = carve_chunk(a, c, B, Tn, Tf, k);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "llm_prefill_chunk: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, D = c.llm_d, M = s.M, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh;
+  const int dt = c.dtype, D = c.llm_d, M = s.M, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads;
   const size_t es = esz(dt);
   hipLaunchKernelGGL(chunk_positions_k, dim3(cdiv(M, 256)), dim3(256), 0, st, positions0, s.pos, B, Tn);
   UVX_LAUNCH_CHECK();
   RC(embed_in(st, c, s.x, inputs_embeds, M));
   UVX_HIP(hipMemsetAsync(k.fq, 0, (size_t)B * Tf * s.QKV * es, st));   // the prefix rows' (skipped) query part stays defined
-  const size_t layer_stride = (size_t)2 * B * Tmax * KVD;  // elements
-  bool n1_ready = false, n2_ready = false;
-  for (int l = 0; l < c.llm_layers; ++l) {
-    const uvx_llm_layer_t& L = w->layers[l];
-    if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, M, D, c.rms_eps, c.llm_flavor));
-    char* ck = at(kv_cache, l * layer_stride, dt);
-    char* cv = at(kv_cache, l * layer_stride + (size_t)B * Tmax * KVD, dt);
-    RC(qkv_rope_append(st, c, w, L, s, s.n, s.pos, B, Tn, Tmax, cur_len, ck, cv, l));
-    const long long ng = (long long)B * Tf * (KVD / 8);
-    if (dt == DT_BF16)
-      hipLaunchKernelGGL(kv_gather_k<bf16_t>, dim3(cdiv(ng, 256)), dim3(256), 0, st, (const bf16_t*)ck, (const bf16_t*)cv, (bf16_t*)k.fq, B, Tf, Tmax, s.QKV, Hq * dh, KVD);
-    else
-      hipLaunchKernelGGL(kv_gather_k<float>, dim3(cdiv(ng, 256)), dim3(256), 0, st, (const float*)ck, (const float*)cv, (float*)k.fq, B, Tf, Tmax, s.QKV, Hq * dh, KVD);
+  RC(infer_layers(st, c, w, s, M, B, Tmax, kv_cache, [&](int l, const uvx_llm_layer_t& L, void* ck, void* cv, bool n1_ready) -> int {
+    RC(qkv_rope_append(st, c, w, L, s, n1_ready, s.pos, B, Tn, Tmax, cur_len, ck, cv, l));
+    launch_kv_gather(st, dt, ck, cv, k.fq, B, Tf, Tmax, s.QKV, Hq * dh, Hkv * dh);
     UVX_LAUNCH_CHECK();
     for (int b = 0; b < B; ++b)   // the new rows' queries into their place in the full-length layout
       UVX_HIP(hipMemcpy2DAsync(at(k.fq, ((size_t)b * Tf + cur_len) * s.QKV, dt), (size_t)s.QKV * es, at(s.qkv, (size_t)b * Tn * s.QKV, dt),
@@ -586,17 +642,12 @@ static int32_t prefill_chunk_impl(void* stream, const uvx_config_t* cfg, const u
     for (int b = 0; b < B; ++b)
       UVX_HIP(hipMemcpyAsync(at(s.o, (size_t)b * Tn * s.OD, dt), at(k.fo, ((size_t)b * Tf + cur_len) * s.OD, dt), (size_t)Tn * s.OD * es,
                              hipMemcpyDeviceToDevice, st));
-    RC(attn_out(st, c, L, s, M, s.o, s.OD, s.x, s.x2, &n2_ready));
-    RC(mlp_block(st, c, L, s, M, s.x2, s.x, n2_ready, l + 1 < c.llm_layers ? w->layers[l + 1].ln1 : nullptr, &n1_ready));
-  }
-  if (all_rows) {      // final norm and LM head on the B * Tn new rows (x2 is free after the last layer)
-    RC(rmsnorm_fwd(st, dt, s.x, w->norm, s.x2, nullptr, M, D, c.rms_eps, c.llm_flavor));
-    return gemm(st, dt, lin(s.x2, w->lm_head, logits_last, M, c.vocab, D));
-  }
-  UVX_HIP(hipMemcpy2DAsync(s.last, (size_t)D * es, at(s.x, (size_t)(Tn - 1) * D, dt), (size_t)Tn * D * es, (size_t)D * es, B,
-                           hipMemcpyDeviceToDevice, st));
-  RC(rmsnorm_fwd(st, dt, s.last, w->norm, s.hn, nullptr, B, D, c.rms_eps, c.llm_flavor));
-  return gemm(st, dt, lin(s.hn, w->lm_head, logits_last, B, c.vocab, D));
+    return UVX_OK;
+  }));
+  if (!all_rows) return head_last(st, c, w, s, B, Tn, logits_last);
+  // final norm and LM head on the B * Tn new rows (x2 is free after the last layer)
+  RC(rmsnorm_fwd(st, dt, s.x, w->norm, s.x2, nullptr, M, D, c.rms_eps, c.llm_flavor));
+  return gemm(st, dt, lin(s.x2, w->lm_head, logits_last, M, c.vocab, D));
 }
 
 extern "C" int32_t uvx_llm_prefill_chunk(void* stream, const uvx_config_t* cfg, const uvx_llm_weights_t* w, const void* inputs_embeds,
@@ -624,77 +675,25 @@ extern "C" int32_t uvx_llm_decode(void* stream, const uvx_config_t* cfg, const u
   Arena a(workspace, ws_bytes);
   InferWs s = carve(a, c, B, 1);
   UVX_CHECK(a.fits(), UVX_ERR_WORKSPACE, "llm_decode: workspace %zu < %zu bytes", ws_bytes, a.off);
-  const int dt = c.dtype, D = c.llm_d, dh = c.llm_head_dim, Hq = c.llm_heads, Hkv = c.llm_kv_heads, KVD = Hkv * dh;
+  const int dt = c.dtype, D = c.llm_d, dh = c.llm_head_dim;
   UVX_CHECK(dh == 64 || dh == 128 || dh == 256, UVX_ERR_UNSUPPORTED, "llm_decode: head_dim %d not supported", dh);
-  RC(gemma3_check(c, w));         // (weights / tables only: the sliding-window layers clamp their key range below)
+  RC(gemma3_check(c, w));         // (weights / tables only: the sliding-window layers clamp their key range in decode_attn)
   RC(embed_in(st, c, s.x, token_embeds, B));
-  const size_t layer_stride = (size_t)2 * B * Tmax * KVD;
-  const float scale = attn_scale_of(c);
-  bool n1_ready = false, n2_ready = false;      // batches beyond 16 rows (tiled split-K linears): the norms ride in the reduce kernels
-  for (int l = 0; l < c.llm_layers; ++l) {
-    const uvx_llm_layer_t& L = w->layers[l];
-    const bool fuse_rope_append = dt == DT_BF16 && !c.llm_qk_norm;     // (Qwen3 / Gemma-3: q_norm / k_norm + RoPE is its own kernel)
-    if (fuse_rope_append) {
-      // input_layernorm inside the q|k|v GEMV (B <= 2); otherwise the two launches
-      GemmDesc g = lin(s.x, L.wqkv, s.qkv, B, s.QKV, D);
-      g.bias = L.bqkv;
-      const int rc = n1_ready ? UVX_ERR_UNSUPPORTED : gemm_skinny_rmsnorm_bf16(st, g, L.ln1, c.rms_eps, c.llm_flavor);
-      if (rc == UVX_ERR_UNSUPPORTED) {
-        if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, B, D, c.rms_eps, c.llm_flavor));
-        g.A = s.n;
-        RC(gemm(st, dt, sk(g, s)));
-      } else {
-        RC(rc);
-      }
-    } else {
+  // (n1_ready - batches beyond 16 rows, tiled split-K linears: the norms ride in the reduce kernels)
+  RC(infer_layers(st, c, w, s, B, B, Tmax, kv_cache, [&](int l, const uvx_llm_layer_t& L, void* ck, void* cv, bool n1_ready) -> int {
+    // raw rows: input_layernorm inside the q|k|v GEMV (B <= 2) / the staged skinny kernel (B <= 16); otherwise the norm, then the projection
+    // - with q / k norms or in f32 followed by the rotation (qkv_rope)
+    GemmDesc g = lin(s.x, L.wqkv, s.qkv, B, s.QKV, D);
+    g.bias = L.bqkv;
+    const int rc = n1_ready || !rope_fusable(c) ? UVX_ERR_UNSUPPORTED : gemm_skinny_rmsnorm_bf16(st, g, L.ln1, c.rms_eps, c.llm_flavor);
+    if (rc != UVX_ERR_UNSUPPORTED) RC(rc);
+    else {
       if (!n1_ready) RC(rmsnorm_fwd(st, dt, s.x, L.ln1, s.n, nullptr, B, D, c.rms_eps, c.llm_flavor));
-      RC(qkv_rope(st, c, w, L, s.n, s.qkv, positions, B, 1, s.QKV, l, &s));
+      if (rope_fusable(c)) { g.A = s.n; RC(gemm(st, dt, sk(g, s))); }
+      else RC(qkv_rope(st, c, w, L, s.n, s.qkv, positions, B, 1, s.QKV, l, &s));
     }
-    const int lo = decode_first_slot(c, w, l, cur_len);      // sliding-window layer: the new token attends to the last `window` cache slots
-    char* ck = at(kv_cache, l * layer_stride, dt);
-    char* cv = at(kv_cache, l * layer_stride + (size_t)B * Tmax * KVD, dt);
-    const long long n = (long long)B * (KVD / 8);
-    const int nw = B * Hq;
-    if (dt == DT_BF16) {
-      const int Gall = Hq / Hkv, len = cur_len + 1;
-      // query heads of a KV head per block: split the group until ~256 blocks are in flight (powers of two that divide the group)
-      int hsplit = 1;
-      while (hsplit * 2 <= Gall && Gall % (hsplit * 2) == 0 && B * Hkv * hsplit < 256) hsplit *= 2;
-      const int G = Gall / hsplit;
-      const size_t sh = sizeof(float) * (size_t)G * len;
-      // the grouped attention kernel rotates q / k and appends the new k / v rows itself (option 23; Gemma-3's local layers have their own table:
-      // they keep the separate launch) - otherwise rope_kv_append_k (or, with q / k norms, kv_append_k after qkv_rope) runs first
-      const bool grp = sh <= 48 * 1024 && ((dh == 128 && (G == 1 || G == 2 || G == 4 || G == 8)) || (dh == 64 && (G == 1 || G == 2 || G == 4)));
-      const bool in_attn = fuse_rope_append && grp && opt(UVX_OPT_DECODE_ROPE_APPEND_SEPARATE) != 1 && c.llm_flavor != UVX_LLM_GEMMA3;
-      const float* rcs = in_attn ? w->rope_cos_sin : nullptr;
-      if (in_attn) {
-      } else if (fuse_rope_append) {
-        launch_rope_kv_append<bf16_t>(st, s.qkv, w->rope_cos_sin, positions, ck, cv, B, 1, Tmax, cur_len, Hq, Hkv, dh, s.QKV);
-      } else {
-        hipLaunchKernelGGL(kv_append_k<bf16_t>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const bf16_t*)s.qkv, (bf16_t*)ck, (bf16_t*)cv, B, 1, Tmax, cur_len, s.QKV, Hq * dh, KVD);
-      }
-#define UVX_DEC(DD, GG) RC((launch_decode_grp<DD, GG>(st, sh, B * Hkv * hsplit, (const bf16_t*)s.qkv, (bf16_t*)ck, (bf16_t*)cv, (bf16_t*)s.o, kv_start, Hq, Hkv, Tmax, len, s.QKV, scale, lo, hsplit, rcs, positions)))
-      if (sh <= 48 * 1024 && dh == 128 && G == 4) UVX_DEC(128, 4);
-      else if (sh <= 48 * 1024 && dh == 128 && G == 8) UVX_DEC(128, 8);
-      else if (sh <= 48 * 1024 && dh == 128 && G == 2) UVX_DEC(128, 2);
-      else if (sh <= 48 * 1024 && dh == 128 && G == 1) UVX_DEC(128, 1);
-      else if (sh <= 48 * 1024 && dh == 64 && G == 4) UVX_DEC(64, 4);
-      else if (sh <= 48 * 1024 && dh == 64 && G == 2) UVX_DEC(64, 2);
-      else if (sh <= 48 * 1024 && dh == 64 && G == 1) UVX_DEC(64, 1);
-#undef UVX_DEC
-      else if (dh == 256) hipLaunchKernelGGL((attn_decode_k<bf16_t, 256>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const bf16_t*)s.qkv, (const bf16_t*)ck, (const bf16_t*)cv, (bf16_t*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-      else if (dh == 64) hipLaunchKernelGGL((attn_decode_k<bf16_t, 64>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const bf16_t*)s.qkv, (const bf16_t*)ck, (const bf16_t*)cv, (bf16_t*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-      else hipLaunchKernelGGL((attn_decode_k<bf16_t, 128>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const bf16_t*)s.qkv, (const bf16_t*)ck, (const bf16_t*)cv, (bf16_t*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-    } else {
-      hipLaunchKernelGGL(kv_append_k<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)s.qkv, (float*)ck, (float*)cv, B, 1, Tmax, cur_len, s.QKV, Hq * dh, KVD);
-      if (dh == 256) hipLaunchKernelGGL((attn_decode_k<float, 256>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const float*)s.qkv, (const float*)ck, (const float*)cv, (float*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-      else if (dh == 64) hipLaunchKernelGGL((attn_decode_k<float, 64>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const float*)s.qkv, (const float*)ck, (const float*)cv, (float*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-      else hipLaunchKernelGGL((attn_decode_k<float, 128>), dim3(cdiv(nw, 4)), dim3(256), 0, st, (const float*)s.qkv, (const float*)ck, (const float*)cv, (float*)s.o, kv_start, B, Hq, Hkv, Tmax, cur_len + 1, s.QKV, scale, lo);
-    }
-    UVX_LAUNCH_CHECK();
-    RC(attn_out(st, c, L, s, B, s.o, s.OD, s.x, s.x2, &n2_ready));
-    RC(mlp_block(st, c, L, s, B, s.x2, s.x, n2_ready, l + 1 < c.llm_layers ? w->layers[l + 1].ln1 : nullptr, &n1_ready));
-  }
+    return decode_attn(st, c, w, s, l, positions, kv_start, ck, cv, B, Tmax, cur_len);
+  }));
   RC(rmsnorm_fwd(st, dt, s.x, w->norm, s.hn, nullptr, B, D, c.rms_eps, c.llm_flavor));
   return gemm(st, dt, sk(lin(s.hn, w->lm_head, logits, B, c.vocab, D), s));
 }

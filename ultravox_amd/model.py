@@ -851,6 +851,28 @@ class UltravoxModel:
         if flag is not None and bool(flag):
             raise ValueError(self._MASK_MSG + " (detected on a device mask of an earlier call)")
 
+    def _regrown_cache(self, cache: torch.Tensor, Tmax: int, new_T: int, B: int, P: int) -> torch.Tensor:
+        """A KV cache of `new_T` positions that keeps rows [0, P) of every (layer, k|v, sequence) plane of `cache` (of `Tmax` positions)."""
+        nbytes = _lib.lib().uvx_kv_cache_bytes(C.byref(self._c), B, new_T)
+        grown = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        planes = self._c.llm_layers * 2 * B                   # (a position: kv_heads * head_dim elements, nbytes // (planes * new_T) bytes)
+        grown.view(planes, new_T, -1)[:, :P].copy_(cache[:nbytes // new_T * Tmax].view(planes, Tmax, -1)[:, :P])
+        return grown
+
+    def _decoder(self, cache, Tmax, kv_start, ws, nb, logits):
+        """The decode step of one generate() run, over what stays in place from token to token (and two buffers of its own, allocated once):
+        step(tokens, positions, cur_len) embeds every row's chosen token and runs uvx_llm_decode on it: cache row `cur_len` -> `logits`."""
+        l, B = _lib.lib(), logits.shape[0]
+        emb = torch.empty(B, self.config.text_config.hidden_size, device=self.device, dtype=self.dtype)
+        offs = torch.empty(B + 1, device=self.device, dtype=torch.int32)
+
+        def step(tokens, positions, cur_len):
+            check(l.uvx_embed_merge(stream_ptr(), C.byref(self._c), ptr(self._llm["embed"]), ptr(tokens), None, None, None,
+                                    None, B, 1, 0, 0, ptr(emb), ptr(offs)), "uvx_embed_merge")
+            check(l.uvx_llm_decode(stream_ptr(), C.byref(self._c), C.byref(self._lw), ptr(emb), ptr(positions), ptr(kv_start),
+                                   ptr(cache), Tmax, cur_len, B, ptr(logits), ptr(ws), C.c_size_t(nb)), "uvx_llm_decode")
+        return step
+
     def _forward_with_cache(self, past, input_ids, inputs_embeds, audio_values, audio_token_start_idx, audio_lens, audio_token_len,
                             audio_batch_size, labels, attention_mask, logits_to_keep) -> CausalLMOutputWithPast:
         """forward(..., past_key_values=KVState) - what the reference forwards to the language model (ultravox_model.py:328-334)
@@ -883,14 +905,9 @@ class UltravoxModel:
         if P + Tn > self._llm["rope_len"]:
             raise ValueError(f"cache + new tokens = {P + Tn} exceeds the RoPE table ({self._llm['rope_len']})")
         cache, Tmax = past.cache, past.Tmax
-        if Tmax < P + Tn:                      # grow: rows [0, P) of every (layer, k|v, sequence) plane move over
+        if Tmax < P + Tn:
             new_T = min(max(P + Tn, 2 * Tmax), self._llm["rope_len"])     # (doubling, but never past the RoPE table the kernels check)
-            nbytes = l.uvx_kv_cache_bytes(C.byref(self._c), B, new_T)
-            grown = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            planes = self._c.llm_layers * 2 * B
-            row = nbytes // (planes * new_T)
-            grown[:nbytes].view(planes, new_T, row)[:, :P].copy_(cache[:planes * Tmax * row].view(planes, Tmax, row)[:, :P])
-            cache, Tmax = grown, new_T
+            cache, Tmax = self._regrown_cache(cache, Tmax, new_T, B, P), new_T
         nb = l.uvx_llm_prefill_chunk_ws_bytes(C.byref(self._c), B, Tn, P)
         ws = self._workspace("infer", nb)
         logits = torch.empty((B, Tn, V) if all_rows else (B, 1, V), device=dev, dtype=self.dtype)
@@ -1190,13 +1207,10 @@ class UltravoxModel:
         pos0 = None if P == 0 else (past.pos_next - (past.cur_len - P)).to(torch.int32).contiguous()
         if P > 0 and P == past.cur_len and past.Tmax >= Tmax:
             cache, Tmax = past.cache, past.Tmax          # append in place (rows below cur_len stay as they are)
+        elif P > 0:
+            cache = self._regrown_cache(past.cache, past.Tmax, Tmax, B, P)
         else:
             cache = (torch.empty(cache_bytes, device=dev, dtype=torch.uint8) if own_cache else self._workspace("kv", cache_bytes))
-            if P > 0:                          # grow: rows [0, P) of every (layer, k|v, sequence) plane move over
-                planes = self._c.llm_layers * 2 * B
-                row = cache_bytes // (planes * Tmax)                      # bytes of one position: kv_heads * head_dim elements
-                cache[:cache_bytes].view(planes, Tmax, row)[:, :P].copy_(
-                    past.cache[:planes * past.Tmax * row].view(planes, past.Tmax, row)[:, :P])
         nb = max(l.uvx_llm_infer_ws_bytes(C.byref(self._c), B, T), l.uvx_llm_infer_ws_bytes(C.byref(self._c), B, 1),
                  l.uvx_llm_prefill_chunk_ws_bytes(C.byref(self._c), B, T - P, P) if P > 0 else 0)
         ws = self._workspace("infer", nb)
@@ -1218,8 +1232,7 @@ class UltravoxModel:
         if streamer is not None:
             streamer.put(input_ids.cpu())
         nxt = torch.empty(B, device=dev, dtype=torch.int64)
-        emb = torch.empty(B, D, device=dev, dtype=self.dtype)
-        offs = torch.empty(B + 1, device=dev, dtype=torch.int32)
+        decode = self._decoder(cache, Tmax, kv_start, ws, nb, logits)
         unfinished = torch.ones(B, device=dev, dtype=torch.bool)
         n_decoded = 0
         # The device loop: choosing the token and the loop's per-token bookkeeping - pad once a sequence has finished, the EOS test, the next RoPE
@@ -1279,10 +1292,7 @@ class UltravoxModel:
                     streamer.put(nxt.cpu())
                 if step + 1 == max_new_tokens or int(counter[step & 1]) == 0:
                     break
-                check(l.uvx_embed_merge(stream_ptr(), C.byref(self._c), ptr(self._llm["embed"]), ptr(nxt), None, None, None,
-                                        None, B, 1, 0, 0, ptr(emb), ptr(offs)), "uvx_embed_merge")
-                check(l.uvx_llm_decode(stream_ptr(), C.byref(self._c), C.byref(self._lw), ptr(emb), ptr(pos), ptr(kv_start),
-                                       ptr(cache), Tmax, T + step, B, ptr(logits), ptr(ws), C.c_size_t(nb)), "uvx_llm_decode")
+                decode(nxt, pos, T + step)
                 n_decoded += 1
             if philox is not None:
                 philox.advance(n_out)
@@ -1307,12 +1317,7 @@ class UltravoxModel:
                 unfinished = unfinished & ~generation.stopped(crit, torch.cat(out, dim=1), logits.float())
             if step + 1 == max_new_tokens or not bool(unfinished.any()):
                 break
-            tok = tok.contiguous()
-            check(l.uvx_embed_merge(stream_ptr(), C.byref(self._c), ptr(self._llm["embed"]), ptr(tok), None, None, None,
-                                    None, B, 1, 0, 0, ptr(emb), ptr(offs)), "uvx_embed_merge")
-            pos = (next_pos + step).contiguous()
-            check(l.uvx_llm_decode(stream_ptr(), C.byref(self._c), C.byref(self._lw), ptr(emb), ptr(pos), ptr(kv_start),
-                                   ptr(cache), Tmax, T + step, B, ptr(logits), ptr(ws), C.c_size_t(nb)), "uvx_llm_decode")
+            decode(tok.contiguous(), (next_pos + step).contiguous(), T + step)
             n_decoded += 1
         if streamer is not None:
             streamer.end()
@@ -1385,8 +1390,7 @@ class UltravoxModel:
         first_nb = (torch.arange(K, device=dev) < nb)[None, :]
         item0 = (torch.arange(B, device=dev) * nb)[:, None]
         identity = torch.arange(BB, device=dev)
-        emb = torch.empty(BB, D, device=dev, dtype=self.dtype)
-        offs = torch.empty(BB + 1, device=dev, dtype=torch.int32)
+        decode = self._decoder(cache, Tmax, kv_start, ws, nbytes, logits)
         take = torch.take_along_dim
         for s in range(Lg):
             logp = torch.log_softmax(logits.float(), dim=-1)
@@ -1437,12 +1441,7 @@ class UltravoxModel:
             cur = T + s                                           # cache rows written so far
             if not still:
                 cv[:, :, :cur] = cv[:, flat, :cur]
-            tok_next = run_seq[:, :, s].reshape(BB).contiguous()
-            check(l.uvx_embed_merge(stream_ptr(), C.byref(self._c), ptr(self._llm["embed"]), ptr(tok_next), None, None, None,
-                                    None, BB, 1, 0, 0, ptr(emb), ptr(offs)), "uvx_embed_merge")
-            pos = (next_pos + s).contiguous()
-            check(l.uvx_llm_decode(stream_ptr(), C.byref(self._c), C.byref(self._lw), ptr(emb), ptr(pos), ptr(kv_start), ptr(cache), Tmax,
-                                   cur, BB, ptr(logits), ptr(ws), C.c_size_t(nbytes)), "uvx_llm_decode")
+            decode(run_seq[:, :, s].reshape(BB).contiguous(), (next_pos + s).contiguous(), cur)
         n = int(fin_len[:, :nrs].max())
         sequences = torch.cat([ids_dev.repeat_interleave(nrs, dim=0), fin_seq[:, :nrs, :n].reshape(B * nrs, n)], dim=1)
         if not return_dict:
