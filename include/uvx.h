@@ -236,6 +236,61 @@ int32_t uvx_wave_norm(void* stream, int32_t pcm_format, const void* pcm, const i
                       int32_t max_n, int32_t normalize, float padding_value, float* out, int64_t out_stride, int32_t out_width,
                       void* workspace, size_t ws_bytes);
 
+/* Audio augmentation of a ragged batch of clips, each row by its own parameters: gain, a recursive (IIR) filter and additive noise at a
+ * signal-to-noise ratio - the arithmetic of the reference's `gain`, `bandpass_filter` / `lowpass_filter` and `colored_noise` augmentations
+ * (ultravox/data/aug/).  The three entries share one layout:
+ *   pcm    the input layout of uvx_resample_poly / uvx_wave_norm: all rows in one device buffer, f32 (pcm_format 0) or int16 (pcm_format 1; a
+ *          sample counts as x * 2^-15, exact).  Row b is the n[b] elements from element row_offset[b] on, at any element offset; n[b] is clamped
+ *          to [0, max_n].
+ *   out    f32, row b at out + b * out_stride; it must not overlap pcm.  Positions [n[b], out_width) are written as 0.0f, elements from
+ *          out_width to the stride are not touched.  A row's bits depend on its samples, n and its own parameters (for the noise: seed, offset
+ *          and b as well) only: not on B, the other rows, row_offset, out_width or out_stride.
+ * All index arithmetic is 64-bit where b * stride can pass 2^31; no floating-point atomics; calls are asynchronous on `stream`.
+ * Status, all three: UVX_ERR_INVALID for a null buffer, a pcm_format other than 0 / 1, B outside [0, 65535], max_n < 0, out_stride < out_width
+ * and out_width < max_n.  B == 0 and out_width == 0 are no-ops.  Covered by tests/test_aug_gpu.py in both formats.
+ *
+ * uvx_aug_gain:  out[b][i] = min(max(fl32(x_i * gain[b]), -1), 1), gain f32 [B] on the device.  The host rounds 10^(gain_db / 20) from float64 to f32
+ * once; numpy computes the same for a float32 clip, so the result is np.clip(x * gain, -1, 1) to the bit.
+ *
+ * uvx_aug_iir:  scipy.signal.lfilter(b, a, x) for a stable filter.  b, a: f64 [order + 1] on the device, normalised to a[0] == 1; 1 <= order
+ * <= 16 (anything else: UVX_ERR_INVALID).  The recurrence is scipy's transposed direct form II in float64, compiled as written,
+ *     y_i = z_0 + b_0 x_i;   z_q = (z_(q+1) + b_(q+1) x_i) - a_(q+1) y_i  for q < order - 1;   z_(order-1) = b_order x_i - a_order y_i,
+ * with one rounding to f32 at the store.  It is parallel in time by warm-up: outputs [256 j, 256 (j + 1)) of a row come from running the
+ * recurrence from zero state at sample max(0, 256 j - warm).  A block with 256 j <= warm starts at sample 0 and is the exact recurrence; any other
+ * has dropped the response to the samples before its start, which `warm` (>= 0, chosen by the host: ultravox_amd.aug.iir_warm_len, the impulse
+ * response's tail below 2^-40 of its absolute sum) bounds.  256 is BLOCK of csrc/aug.h.
+ *
+ * uvx_aug_noise:  out_i = (float)((double)x_i + (double)noise_i * scale) with noise of the given colour (0 white, 1 pink, 2 brown, 3 blue,
+ * 4 violet; anything else: UVX_ERR_INVALID) and scale = sqrt((S2x / n) * noise_ratio[b] / (S2n / n)); noise_ratio f64 [B] on the device,
+ * 10^(-snr_db / 10) from the host.  S2x and S2n are the float64 sums of x_i^2 and noise_i^2 over the row in uvx_wave_norm's order (chunks of
+ * 16 384 samples, 256 strided partial sums, a halving tree, chunks in ascending order).  If S2x or S2n is 0 the row is copied unchanged (the
+ * reference gives the same for a silent clip).
+ *   normals  normal number m of row b comes from Philox4x32-10 under key (seed_lo, seed_hi) and counter (offset_lo, offset_hi, m >> 2, b).  With
+ *          the output words w0 .. w3, lanes 0 and 1 are r cos(2 pi v) and r sin(2 pi v) with r = sqrt(-2 ln u), u = ((w0 >> 9) + 0.5) * 2^-23 (24
+ *          significant bits, never 0 or 1) and v = (w1 >> 8) * 2^-24; lanes 2 and 3 are the same from (w2, w3).  Evaluated in f32.  The caller
+ *          advances `offset` by one per launch.
+ *   white    noise_i = normal i.
+ *   coloured M = max(2, smallest power of two >= n[b]).  Spectrum for k = 0 .. M / 2: Z_k = (g_2k + i g_(2k+1)) * sqrt(M / 2) from the normals
+ *          g; Z_0 and Z_(M/2) are real, g_2k * sqrt(M), the odd normal drawn and dropped.  f_k = k / M, f_0 := f_1.  Amplitude factors: pink
+ *          f^-1/2, brown f^-1, blue f^1/2, violet f.  The noise is the first n samples of the length-M real inverse DFT (with its 1 / M) of the
+ *          Hermitian extension of Z_k * factor(f_k), in f32.  n == 1 works (M = 2).  Limit: max_n <= 2^21, beyond it UVX_ERR_UNSUPPORTED with
+ *          the limit in the message; white noise has no limit.
+ *   law      the reference draws white noise in time, runs an FFT of length n, shapes it with the same factors on the grid k / n and runs an
+ *          inverse FFT of length n.  The transform of white Gaussian noise is the spectrum above in law, so no forward transform runs here.
+ *          What differs is the frequency grid (M points instead of n) and with it the circular period (M instead of n): a difference in law
+ *          of the size of the grid spacing, not in kind.  The draws themselves could never equal numpy's Mersenne Twister.
+ *   workspace  uvx_aug_noise_ws_bytes(B, max_n, colour) = B * (ceil(max_n / 16384) * 16 + (colour ? M(max_n) / 2 * 8 : 0)) bytes (0 for B <= 0 or
+ *          max_n <= 0), 16-byte aligned; a null workspace or ws_bytes below that size, when it is not 0: UVX_ERR_INVALID.
+ * The transform is this library's own (csrc/aug_fft.hip; its pass structure and LDS span are stated in csrc/aug.h). */
+int32_t uvx_aug_gain(void* stream, int32_t pcm_format, const void* pcm, const int64_t* row_offset, const int32_t* n, int32_t B, int32_t max_n,
+                     const float* gain, float* out, int64_t out_stride, int32_t out_width);
+int32_t uvx_aug_iir(void* stream, int32_t pcm_format, const void* pcm, const int64_t* row_offset, const int32_t* n, int32_t B, int32_t max_n,
+                    const double* b, const double* a, int32_t order, int32_t warm, float* out, int64_t out_stride, int32_t out_width);
+size_t uvx_aug_noise_ws_bytes(int32_t B, int32_t max_n, int32_t colour);
+int32_t uvx_aug_noise(void* stream, int32_t pcm_format, const void* pcm, const int64_t* row_offset, const int32_t* n, int32_t B, int32_t max_n,
+                      int32_t colour, const double* noise_ratio, uint64_t seed, uint64_t offset, float* out, int64_t out_stride,
+                      int32_t out_width, void* workspace, size_t ws_bytes);
+
 /* ModifiedWhisperEncoder.forward (ultravox_model.py:865-994), inference mode (frozen tower).
  * mel [B, n_mels, F] (f32 if mel_is_f32 else cfg dtype; cast like ultravox_model.py:383);
  * audio_lens [B] int64 mel-frame lengths or NULL (no padding mask); out [B, Te, d], Te = (F-1)/2+1. */

@@ -234,7 +234,7 @@ class AttnDesc(C.Structure):
 
 
 EXPORTS = [
-    "uvx_last_error", "uvx_abi_version", "uvx_logmel", "uvx_resample_poly", "uvx_wave_norm_ws_bytes", "uvx_wave_norm", "uvx_encoder_ws_bytes", "uvx_encoder_fwd",
+    "uvx_last_error", "uvx_abi_version", "uvx_logmel", "uvx_resample_poly", "uvx_wave_norm_ws_bytes", "uvx_wave_norm", "uvx_aug_gain", "uvx_aug_iir", "uvx_aug_noise_ws_bytes", "uvx_aug_noise", "uvx_encoder_ws_bytes", "uvx_encoder_fwd",
     "uvx_projector_ws_bytes", "uvx_projector_fwd", "uvx_projector_bwd", "uvx_embed_merge", "uvx_merge_embeds_bwd",
     "uvx_llm_ws_bytes", "uvx_llm_fwd", "uvx_llm_bwd", "uvx_adamw_clip_step", "uvx_gemm", "uvx_layernorm",
     "uvx_rmsnorm", "uvx_gemm_rmsnorm", "uvx_rmsnorm_bwd", "uvx_swiglu", "uvx_swiglu_bwd", "uvx_rope", "uvx_qk_norm_rope", "uvx_qk_norm_bwd", "uvx_attention_ws_bytes",
@@ -252,7 +252,7 @@ EXPORTS = [
 def _declare(l: C.CDLL) -> None:
     for name in ("uvx_encoder_ws_bytes", "uvx_projector_ws_bytes", "uvx_llm_ws_bytes", "uvx_attention_ws_bytes",
                  "uvx_kv_cache_bytes", "uvx_llm_infer_ws_bytes", "uvx_llm_prefill_chunk_ws_bytes", "uvx_encoder_train_ws_bytes",
-                 "uvx_wav2vec2_ws_bytes", "uvx_wav2vec2_train_ws_bytes", "uvx_gemm_splitk_ws_bytes", "uvx_wave_norm_ws_bytes"):
+                 "uvx_wav2vec2_ws_bytes", "uvx_wav2vec2_train_ws_bytes", "uvx_gemm_splitk_ws_bytes", "uvx_wave_norm_ws_bytes", "uvx_aug_noise_ws_bytes"):
         getattr(l, name).restype = C.c_size_t
     for name in EXPORTS:
         f = getattr(l, name)
@@ -268,6 +268,10 @@ def _declare(l: C.CDLL) -> None:
     l.uvx_resample_poly.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, i64, i32]
     l.uvx_wave_norm_ws_bytes.argtypes = [i32, i32]
     l.uvx_wave_norm.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, i64, i32, vp, C.c_size_t]
+    l.uvx_aug_gain.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, i64, i32]
+    l.uvx_aug_iir.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, i32]
+    l.uvx_aug_noise_ws_bytes.argtypes = [i32, i32, i32]
+    l.uvx_aug_noise.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, u64, u64, vp, i64, i32, vp, C.c_size_t]
     l.uvx_seen_mark.argtypes = [vp, vp, i64, i32, i32, i32, vp, i32]
     l.uvx_greedy_select_penalized.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, vp, vp, i32, i64, vp, vp, vp, i64, i64, vp, vp, i32, vp]
     l.uvx_sample_select_penalized.argtypes = [vp, i32, vp, i32, i32, f32, vp, i32, f32, i32, f32, f32, i32, u64, u64, vp, vp, vp, i32, i64, vp, vp, vp, i64, i64,

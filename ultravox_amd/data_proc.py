@@ -66,7 +66,9 @@ class UltravoxDataproc:
             sample = copy.copy(sample)
             sample.messages = sample.messages[:-1]
         text = self._template(sample.messages)
-        audio = np.expand_dims(sample.audio, axis=0) if sample.audio is not None else None      # [channels = 1, samples]
+        audio = sample.audio                                                                    # [channels = 1, samples]
+        if audio is not None:      # (a clip an augmentation left on the GPU is a tensor and stays there)
+            audio = audio[None] if getattr(audio, "is_cuda", False) else np.expand_dims(audio, axis=0)
         inputs = self.processor(text=text, audios=audio, return_tensors="pt", sampling_rate=sample.sample_rate)
         input_ids = inputs["input_ids"] = inputs["input_ids"].squeeze(0)
         inputs["attention_mask"] = inputs["attention_mask"].squeeze(0)

@@ -499,3 +499,77 @@ def wave_norm(pcm, row_offset, n, *, max_n, normalize=True, padding_value=0.0, o
                           float(padding_value), ptr(out), out.stride(0) if B > 1 else max(out.stride(0), out.shape[1]), int(out_width), ptr(ws),
                           ws_bytes), "uvx_wave_norm")
     return out
+
+
+AUG_IIR_BLOCK = 256          # outputs one filter thread produces after its warm-up: BLOCK of csrc/aug.h
+AUG_IIR_MAX_ORDER = 16       # MAX_ORDER of csrc/aug.h
+AUG_FFT_LDS_SPAN = 4096      # complex elements of the noise transform held in LDS: LDS_SPAN of csrc/aug.h (M <= 2 * span needs no global pass)
+AUG_NOISE_MAX_N = 1 << 21    # coloured noise: the longest row (2^MAX_LOG2_M of csrc/aug.h)
+AUG_COLOURS = {"white": 0, "pink": 1, "brown": 2, "blue": 3, "violet": 4}
+
+
+def _aug_layout(what, pcm, row_offset, n, max_n, out, out_width):
+    """The argument checks and the output buffer the three uvx_aug_* wrappers share (wave_norm's layout).  -> (B, out, out_width, stride)"""
+    if pcm.dtype not in (torch.int16, torch.float32) or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise ValueError(f"{what}: pcm has to be a contiguous 1-D int16 or float32 tensor, but is {pcm.dtype} {tuple(pcm.shape)}")
+    if row_offset.dtype != torch.int64 or n.dtype != torch.int32 or row_offset.shape != n.shape or n.dim() != 1:
+        raise ValueError(f"{what}: row_offset has to be int64 [B] and n int32 [B]")
+    B = n.shape[0]
+    if out_width is None:
+        out_width = int(max_n) if out is None or out.dim() != 2 else out.shape[1]
+    if out is None:
+        out = torch.empty(B, out_width, device=pcm.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < out_width or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"{what}: out has to be f32 [B, >= out_width] with unit stride along a row, but is {out.dtype} {tuple(out.shape)}")
+    return B, out, int(out_width), (out.stride(0) if B > 1 else max(out.stride(0), out.shape[1]))
+
+
+def _aug_per_row(what, name, t, dtype, B, device):
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t, dtype=dtype).reshape(-1).to(device)
+    if t.dtype != dtype or t.shape != (B,) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{what}: {name} has to be a contiguous {dtype} [B] tensor on the clips' device, but is {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def aug_gain(pcm, row_offset, n, gain, *, max_n, out=None, out_width=None):
+    """uvx_aug_gain (include/uvx.h): out[b][i] = clip(x_i * gain[b], -1, 1), zero beyond n[b].  pcm, row_offset, n, max_n, out, out_width: as for
+    wave_norm.  gain: f32 [B] (a device tensor, or host numbers that go up here).  -> out"""
+    B, out, out_width, stride = _aug_layout("aug_gain", pcm, row_offset, n, max_n, out, out_width)
+    if B == 0:
+        return out
+    gain = _aug_per_row("aug_gain", "gain", gain, torch.float32, B, pcm.device)
+    check(_lib.lib().uvx_aug_gain(stream_ptr(), 1 if pcm.dtype == torch.int16 else 0, ptr(pcm), ptr(row_offset), ptr(n), B, int(max_n), ptr(gain),
+                                  ptr(out), stride, out_width), "uvx_aug_gain")
+    return out
+
+
+def aug_iir(pcm, row_offset, n, b, a, warm, *, max_n, out=None, out_width=None):
+    """uvx_aug_iir (include/uvx.h): scipy.signal.lfilter(b, a, x) per row by warm-up blocks.  b, a: f64 [order + 1] device tensors with a[0] == 1
+    (the caller normalises); warm: the look-back in samples (ultravox_amd.aug.iir_warm_len).  -> out"""
+    B, out, out_width, stride = _aug_layout("aug_iir", pcm, row_offset, n, max_n, out, out_width)
+    if b.dtype != torch.float64 or a.dtype != torch.float64 or b.dim() != 1 or b.shape != a.shape or b.device != pcm.device or a.device != pcm.device \
+            or not (b.is_contiguous() and a.is_contiguous()):
+        raise ValueError("aug_iir: b and a have to be contiguous float64 [order + 1] tensors on the clips' device")
+    if B == 0:
+        return out
+    check(_lib.lib().uvx_aug_iir(stream_ptr(), 1 if pcm.dtype == torch.int16 else 0, ptr(pcm), ptr(row_offset), ptr(n), B, int(max_n), ptr(b), ptr(a),
+                                 b.shape[0] - 1, int(warm), ptr(out), stride, out_width), "uvx_aug_iir")
+    return out
+
+
+def aug_noise(pcm, row_offset, n, noise_ratio, *, colour, seed, offset, max_n, out=None, out_width=None):
+    """uvx_aug_noise (include/uvx.h): adds noise of `colour` (a name of AUG_COLOURS or its number) at noise_ratio[b] = 10^(-snr_db / 10) times the
+    row's own power.  noise_ratio: f64 [B] (a device tensor, or host numbers that go up here).  The workspace is allocated here.  -> out"""
+    colour = AUG_COLOURS[colour] if isinstance(colour, str) else int(colour)
+    B, out, out_width, stride = _aug_layout("aug_noise", pcm, row_offset, n, max_n, out, out_width)
+    if B == 0:
+        return out
+    noise_ratio = _aug_per_row("aug_noise", "noise_ratio", noise_ratio, torch.float64, B, pcm.device)
+    l = _lib.lib()
+    ws_bytes = int(l.uvx_aug_noise_ws_bytes(B, int(max_n), colour))
+    ws = torch.empty(ws_bytes, device=pcm.device, dtype=torch.uint8) if ws_bytes else None
+    check(l.uvx_aug_noise(stream_ptr(), 1 if pcm.dtype == torch.int16 else 0, ptr(pcm), ptr(row_offset), ptr(n), B, int(max_n), colour,
+                          ptr(noise_ratio), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(out), stride, out_width, ptr(ws), ws_bytes),
+          "uvx_aug_noise")
+    return out
